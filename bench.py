@@ -16,6 +16,12 @@ Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. ``--dump-outputs DIR`` also writes what the last timed step computed as
+``DIR/<name>.npy`` (inputs and weights are seeded, so two builds can be
+compared output for output). ``--full`` is where any measurement beyond the
+headline figure belongs; there is none today.
 """
 
 from __future__ import annotations
@@ -49,7 +55,50 @@ def parse_args() -> argparse.Namespace:
                    default="auto",
                    help="activation checkpointing; auto = off for <=8B on "
                         "MI355X (288 GB HBM fits the full activations), on for 70B")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step "
+                        "computed (loss, sampled gradients and updated "
+                        "parameters) to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure "
+                        "(none yet: a plain run already does only setup, "
+                        "warmup and the timed steps)")
     return p.parse_args()
+
+
+# elements sampled per parameter tensor by --dump-outputs: Llama-3-8B has 291
+# parameter tensors, so params + grads come to ~11 MB of float32 (70B: under 48 MB)
+DUMP_SAMPLE = 8192
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir: str, loss: float, model: torch.nn.Module) -> None:
+    """Write the last timed step's results as float32 .npy files: the loss,
+    and a fixed seeded sample of every parameter's gradient and updated
+    value (FSDP-sharded parameters contribute their local shard)."""
+    import numpy as np
+
+    from torchft_amd.ops import _local_view
+
+    os.makedirs(out_dir, exist_ok=True)
+    gen = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    params, grads = [], []
+    for _, p in sorted(model.named_parameters(), key=lambda kv: kv[0]):
+        w = _local_view(p.detach()).reshape(-1)
+        n = w.numel()
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=gen).to(w.device)
+        else:
+            idx = torch.arange(n, device=w.device)
+        params.append(w[idx].float().cpu())
+        g = p.grad
+        grads.append(
+            _local_view(g.detach()).reshape(-1)[idx].float().cpu()
+            if g is not None else torch.zeros(idx.numel())
+        )
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float32))
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(params).numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), torch.cat(grads).numpy())
 
 
 def main() -> None:
@@ -150,7 +199,11 @@ def main() -> None:
         ckpt = args.model == "llama3_70b" or args.quantize
     else:
         ckpt = args.checkpoint_activations == "on"
-    model = Llama(cfg, dtype=dtype, checkpoint_activations=ckpt)
+    # allocate and initialise the weights on the device: filling 8B
+    # parameters on the host took minutes of every run. manual_seed above
+    # seeds the device generator too, so the init is the same every run.
+    with device:
+        model = Llama(cfg, dtype=dtype, checkpoint_activations=ckpt)
     model = model.to(device)
 
     # ---- fault-tolerance control plane ------------------------------------
@@ -289,6 +342,9 @@ def main() -> None:
     tokens_total = args.batch * seq * world * args.steps
     tok_s = tokens_total / elapsed
     ms_per_step = elapsed / args.steps * 1000
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
 
     if rank == 0:
         result = {

@@ -17,12 +17,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.timeout(300)
-def test_bench_json_contract_cpu():
+def test_bench_json_contract_cpu(tmp_path):
+    dump_dir = tmp_path / "outputs"
     proc = subprocess.run(
         [
             sys.executable, os.path.join(REPO, "bench.py"),
             "--model", "debug", "--steps", "2", "--warmup", "1",
             "--batch", "1", "--seq", "64",
+            "--dump-outputs", str(dump_dir),
         ],
         cwd=REPO,
         capture_output=True,
@@ -53,3 +55,16 @@ def test_bench_json_contract_cpu():
     assert cfg["fault_tolerance"] is True
     # the FT path really ran: a finite loss came through the managed step
     assert isinstance(cfg["loss"], float) and cfg["loss"] == cfg["loss"]
+
+    # --dump-outputs: the last timed step's results as float .npy files
+    import numpy as np
+
+    dumped = {f.stem: np.load(f) for f in dump_dir.glob("*.npy")}
+    assert set(dumped) == {"loss", "params_sample", "grads_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in dumped.values())
+    assert sum(a.nbytes for a in dumped.values()) <= 64 * 2**20
+    assert dumped["loss"].shape == (1,) and dumped["loss"][0] == cfg["loss"]
+    assert dumped["params_sample"].shape == dumped["grads_sample"].shape
+    assert np.isfinite(dumped["params_sample"]).all()
+    assert np.isfinite(dumped["grads_sample"]).all()
+    assert np.abs(dumped["grads_sample"]).max() > 0

@@ -94,6 +94,9 @@ def test_launcher_two_replica_groups():
         capture_output=True,
         text=True,
         timeout=280,
+        # a CPU (gloo) run on every host: both groups would otherwise pick
+        # device 0, and RCCL refuses two ranks of one communicator on one GPU
+        env={**os.environ, "HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""},
     )
     assert proc.returncode == 0, (
         f"launcher failed:\n{proc.stderr[-3000:]}\n{proc.stdout[-1000:]}"

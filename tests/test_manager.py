@@ -509,15 +509,18 @@ class TestQuantizedFallback:
         client = MagicMock()
         client._quorum.return_value = mock_quorum()
         client.should_commit.return_value = True
-        m = make_manager(client, should_quantize=True)
-        try:
-            m.start_quorum()
-            t = torch.ones(4)
-            assert m.allreduce(t).wait()
-            torch.testing.assert_close(t, torch.full((4,), 0.5))  # AVG by 2
-            assert m.should_commit()
-        finally:
-            m.shutdown(wait=False)
+        # present a CPU host for the Manager's whole life, wherever the
+        # suite runs
+        with patch.object(torch.cuda, "is_available", return_value=False):
+            m = make_manager(client, should_quantize=True)
+            try:
+                m.start_quorum()
+                t = torch.ones(4)
+                assert m.allreduce(t).wait()
+                torch.testing.assert_close(t, torch.full((4,), 0.5))  # AVG by 2
+                assert m.should_commit()
+            finally:
+                m.shutdown(wait=False)
 
 
 class TestManagerLifecycleHygiene:
