@@ -360,6 +360,40 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   return {dq, dk, dv};
 }
 
+// ---- fused cross-entropy ------------------------------------------------------
+
+// Per-row loss (fp32 [R]); with write_grad the bf16 logits are overwritten
+// in place by grad_scale * d(row_loss)/d(logits).
+at::Tensor cross_entropy_fwd_bwd(at::Tensor logits, at::Tensor targets,
+                                 int64_t ignore_index, double z_loss,
+                                 at::Tensor grad_scale, bool write_grad) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
+                  logits.dim() == 2,
+              "logits must be a bf16 [R, V] device tensor");
+  TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous (row stride == V)");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (int64_t(1) << 31), "vocab size out of range: ", V);
+  TORCH_CHECK(R < (int64_t(1) << 31), "too many rows for one launch: ", R);
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == at::kLong &&
+                  targets.dim() == 1 && targets.size(0) == R &&
+                  targets.is_contiguous(),
+              "targets must be a contiguous int64 [R] device tensor");
+  TORCH_CHECK(grad_scale.is_cuda() && grad_scale.scalar_type() == at::kFloat &&
+                  grad_scale.numel() == 1,
+              "grad_scale must be a 1-element fp32 device tensor");
+  TORCH_CHECK(targets.device() == logits.device() &&
+                  grad_scale.device() == logits.device(),
+              "all tensors must be on the same device");
+  TORCH_CHECK(z_loss >= 0.0, "z_loss must be >= 0");
+  auto row_loss = at::empty({R}, logits.options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentCUDAStream().stream();
+  tft::launch_cross_entropy(logits.data_ptr(), targets.data_ptr<int64_t>(),
+                            row_loss.data_ptr<float>(),
+                            grad_scale.data_ptr<float>(), R, (int)V, ignore_index,
+                            (float)z_loss, write_grad, (tft_stream)stream);
+  return row_loss;
+}
+
 at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
   TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kBFloat16);
   TORCH_CHECK(A.sizes() == at::IntArrayRef({32, 16}) &&
@@ -390,6 +424,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_delta", &fa_delta);
   m.def("fa_bwd", &fa_bwd,
         "flash-attention backward (bf16, D=128): returns (dq, dk, dv)");
+  m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd,
+        "fused cross-entropy: returns row_loss, writes the gradient in place");
   m.def("mfma_probe", &mfma_probe, "mfma_f32_32x32x16_bf16 layout probe");
 }
 

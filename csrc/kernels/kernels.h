@@ -71,6 +71,14 @@ void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout
                    void* dv, int B, int Hq, int Hkv, int S, float scale,
                    bool causal, bool bshd, tft_stream stream);
 
+// fused_cross_entropy.hip ---------------------------------------------------
+// logits: bf16 [rows, V] contiguous, overwritten with the gradient when
+// write_grad; grad_scale: one fp32 on the device.
+void launch_cross_entropy(void* logits, const int64_t* targets, float* row_loss,
+                          const float* grad_scale, int64_t rows, int V,
+                          int64_t ignore_index, float z_loss, bool write_grad,
+                          tft_stream stream);
+
 // mfma_probe.hip ------------------------------------------------------------
 void launch_mfma_probe(const void* A, const void* B, float* D, tft_stream s);
 

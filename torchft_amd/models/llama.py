@@ -10,6 +10,7 @@ activation checkpointing sized for 288 GB HBM3E.
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -17,8 +18,18 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from torchft_amd.ops import RMSNorm, rope, rope_tables, swiglu_glu
+from torchft_amd.ops import RMSNorm, linear_cross_entropy, rope, rope_tables, swiglu_glu
 from torchft_amd.ops.flash_attention import flash_attention
+
+
+_ENV_FUSED_CE = "TORCHFT_AMD_FUSED_CE"
+
+
+def fused_ce_enabled() -> bool:
+    """The fused linear + cross-entropy head (opt-in: it changes the loss
+    numerics from bf16-rounded to fp32)."""
+    v = os.environ.get(_ENV_FUSED_CE, "0")
+    return v in ("1", "true", "True")
 
 
 @dataclass
@@ -191,13 +202,35 @@ class Llama(nn.Module):
         tokens: torch.Tensor,
         targets: torch.Tensor,
         chunk_rows: int = 4096,
+        *,
+        fused: Optional[bool] = None,
+        ignore_index: int = -100,
+        z_loss: float = 0.0,
     ) -> torch.Tensor:
         """Mean cross-entropy with chunked logits: the [B*S, vocab] logits
         matrix (2 GB+ at 128k vocab) is computed ``chunk_rows`` rows at a
-        time so peak memory stays bounded."""
+        time so peak memory stays bounded.
+
+        ``fused=True`` (or TORCHFT_AMD_FUSED_CE=1 with ``fused=None``) routes
+        the head through ``ops.linear_cross_entropy``: fp32 loss, memory
+        bounded in training as well (the unfused loop keeps every chunk's
+        bf16 log-probabilities alive until backward), and the only path
+        that supports ``ignore_index`` masking and ``z_loss``."""
+        if fused is None:
+            fused = fused_ce_enabled()
+        if not fused and (ignore_index != -100 or z_loss != 0.0):
+            raise ValueError(
+                "ignore_index and z_loss need the fused cross-entropy head "
+                "(fused=True or TORCHFT_AMD_FUSED_CE=1)"
+            )
         h = self.forward_hidden(tokens)
         h = h.reshape(-1, self.cfg.dim)
         t = targets.reshape(-1)
+        if fused:
+            return linear_cross_entropy(
+                h, self.output.weight, t, chunk_rows=chunk_rows,
+                ignore_index=ignore_index, z_loss=z_loss,
+            )
         n = h.shape[0]
         losses = []
         for i in range(0, n, chunk_rows):

@@ -273,3 +273,9 @@ class FusedAdamW(torch.optim.Optimizer):
                         update = (m / bc1) / denom + group["weight_decay"] * p.float()
                         p.add_((-group["lr"] * update).to(p.dtype))
         return None
+
+
+# ----------------------------------------------------------------- Cross-entropy
+
+# at the bottom: cross_entropy.py imports hip_ext from this module
+from torchft_amd.ops.cross_entropy import linear_cross_entropy  # noqa: E402,F401
