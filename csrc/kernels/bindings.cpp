@@ -4,6 +4,7 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include <vector>
@@ -266,6 +267,241 @@ void adamw_step(const std::vector<at::Tensor>& params,
                     (float)weight_decay, bc1, bc2, (tft_stream)stream);
 }
 
+// ---- global gradient norm / clip ---------------------------------------------
+
+namespace {
+
+// One device table per call: for every dtype present, [ptrs | numels |
+// block_prefix (n+1)] back to back, built in pinned memory and copied once.
+struct GradGroup {
+  int code = 0;  // dtype_code of kernels.h
+  std::vector<const at::Tensor*> ts;
+  int64_t off = 0;     // first int64 of this group's table
+  int64_t blocks = 0;  // logical 2048-element blocks
+};
+
+struct GradTables {
+  at::Tensor dev;
+  std::vector<GradGroup> groups;
+};
+
+GradTables build_grad_tables(const std::vector<at::Tensor>& tensors) {
+  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
+  GradTables tb;
+  tb.groups.resize(3);
+  for (int c = 0; c < 3; c++) tb.groups[c].code = c;
+  for (auto& t : tensors) {
+    TORCH_CHECK(t.is_cuda(), "grad norm requires device tensors");
+    TORCH_CHECK(t.device() == tensors[0].device(), "tensors on different devices");
+    TORCH_CHECK(t.is_contiguous(), "grad norm requires contiguous tensors");
+    auto st = t.scalar_type();
+    int code = st == at::kBFloat16 ? 0 : st == at::kHalf ? 1 : st == at::kFloat ? 2 : -1;
+    TORCH_CHECK(code >= 0, "unsupported dtype for grad norm: ", st);
+    if (t.numel() > 0) tb.groups[code].ts.push_back(&t);
+  }
+  int64_t words = 0;
+  for (auto& g : tb.groups) {
+    g.off = words;
+    if (!g.ts.empty()) words += 3 * (int64_t)g.ts.size() + 1;
+  }
+  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
+  at::Tensor host = at::empty({std::max<int64_t>(words, 1)}, opts);
+  int64_t* h = host.data_ptr<int64_t>();
+  for (auto& g : tb.groups) {
+    const int64_t n = (int64_t)g.ts.size();
+    int64_t* ptrs = h + g.off;
+    int64_t* numels = ptrs + n;
+    int64_t* prefix = numels + n;
+    int64_t acc = 0;
+    for (int64_t i = 0; i < n; i++) {
+      ptrs[i] = (int64_t)g.ts[i]->data_ptr();
+      numels[i] = g.ts[i]->numel();
+      prefix[i] = acc;
+      acc += (g.ts[i]->numel() + kQBlock - 1) / kQBlock;
+    }
+    if (n > 0) prefix[n] = acc;
+    g.blocks = acc;
+  }
+  tb.dev = host.to(tensors[0].device(), /*non_blocking=*/true);
+  return tb;
+}
+
+void check_max_blocks(int64_t max_blocks) {
+  TORCH_CHECK(max_blocks >= 1 && max_blocks <= (int64_t(1) << 16),
+              "max_blocks must be in [1, 65536], got ", max_blocks);
+}
+
+// partial sums per dtype group into one partials buffer, then one finalize
+void run_sumsq(const GradTables& tb, int64_t max_blocks, at::Tensor& stats,
+               tft_stream stream) {
+  int64_t n_partials = 0;
+  for (auto& g : tb.groups) n_partials += std::min(g.blocks, max_blocks);
+  auto partials = at::empty({n_partials}, stats.options());
+  const int64_t* d = tb.dev.data_ptr<int64_t>();
+  int64_t at_partial = 0;
+  for (auto& g : tb.groups) {
+    const int64_t n = (int64_t)g.ts.size();
+    const int64_t grid = std::min(g.blocks, max_blocks);
+    if (grid == 0) continue;
+    const int64_t* base = d + g.off;
+    tft::launch_grad_sumsq_partial(g.code, base, base + n, base + 2 * n, (int)n,
+                                   g.blocks, (int)grid,
+                                   partials.data_ptr<float>() + at_partial, stream);
+    at_partial += grid;
+  }
+  tft::launch_grad_sumsq_finalize(partials.data_ptr<float>(), (int)n_partials,
+                                  stats.data_ptr<float>(), stream);
+}
+
+}  // namespace
+
+// Sum of squares over every tensor, as a 1-element fp32 device tensor.
+at::Tensor grad_sumsq(const std::vector<at::Tensor>& tensors, int64_t max_blocks) {
+  check_max_blocks(max_blocks);
+  auto tb = build_grad_tables(tensors);
+  auto stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentCUDAStream().stream();
+  run_sumsq(tb, max_blocks, stats, (tft_stream)stream);
+  return stats;
+}
+
+// Norm + in-place scale sharing one table; norm_reduce (or None) sees the
+// 1-element sum of squares between the two. Returns the sum of squares.
+at::Tensor clip_grad_norm(const std::vector<at::Tensor>& tensors, double max_norm,
+                          int64_t max_blocks, py::object norm_reduce) {
+  check_max_blocks(max_blocks);
+  TORCH_CHECK(max_norm > 0.0, "max_norm must be > 0");
+  auto tb = build_grad_tables(tensors);
+  auto stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
+  auto stream = at::cuda::getCurrentCUDAStream().stream();
+  run_sumsq(tb, max_blocks, stats, (tft_stream)stream);
+  if (!norm_reduce.is_none()) norm_reduce(stats);
+  const int64_t* d = tb.dev.data_ptr<int64_t>();
+  for (auto& g : tb.groups) {
+    const int64_t n = (int64_t)g.ts.size();
+    if (n == 0) continue;
+    const int64_t* base = d + g.off;
+    tft::launch_grad_scale(g.code, base, base + n, base + 2 * n, (int)n, g.blocks,
+                           stats.data_ptr<float>(), (float)max_norm,
+                           (tft_stream)stream);
+  }
+  return stats;
+}
+
+// FusedAdamW clip mode, one call per optimizer step. The tensor lists are flat
+// over all param groups (group_sizes says how they split); the norm is global,
+// then each group gets one update launch, then one launch bumps the device
+// step counts (finite norm) or the skipped counter (non-finite).
+void adamw_clip_step(const std::vector<at::Tensor>& params,
+                     const std::vector<at::Tensor>& grads,
+                     const std::vector<at::Tensor>& exp_avgs,
+                     const std::vector<at::Tensor>& exp_avg_sqs,
+                     const std::vector<at::Tensor>& steps,
+                     const std::vector<int64_t>& group_sizes,
+                     const std::vector<double>& lrs,
+                     const std::vector<double>& beta1s,
+                     const std::vector<double>& beta2s,
+                     const std::vector<double>& epss,
+                     const std::vector<double>& weight_decays, double max_norm,
+                     int64_t max_blocks, at::Tensor stats, at::Tensor skipped,
+                     at::Tensor norm_out, py::object norm_reduce) {
+  const int64_t n = (int64_t)params.size();
+  const int64_t ng = (int64_t)group_sizes.size();
+  TORCH_CHECK(n > 0);
+  TORCH_CHECK((int64_t)grads.size() == n && (int64_t)exp_avgs.size() == n &&
+              (int64_t)exp_avg_sqs.size() == n && (int64_t)steps.size() == n);
+  TORCH_CHECK((int64_t)lrs.size() == ng && (int64_t)beta1s.size() == ng &&
+              (int64_t)beta2s.size() == ng && (int64_t)epss.size() == ng &&
+              (int64_t)weight_decays.size() == ng);
+  check_max_blocks(max_blocks);
+  TORCH_CHECK(max_norm > 0.0, "max_grad_norm must be > 0");
+  const auto dev = params[0].device();
+  TORCH_CHECK(stats.device() == dev && stats.scalar_type() == at::kFloat &&
+              stats.numel() >= 1 && stats.is_contiguous());
+  TORCH_CHECK(norm_out.device() == dev && norm_out.scalar_type() == at::kFloat &&
+              norm_out.numel() == 1);
+  TORCH_CHECK(skipped.device() == dev && skipped.scalar_type() == at::kInt &&
+              skipped.numel() == 1);
+
+  // [param | grad | m | v | numel | step | prefix over all (n+1) |
+  //  per-group prefixes (size_g + 1 each)]
+  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
+  at::Tensor host = at::empty({8 * n + 1 + ng}, opts);
+  int64_t* h = host.data_ptr<int64_t>();
+  int64_t* gprefix = h + 6 * n;
+  int64_t* uprefix = h + 7 * n + 1;
+  int64_t acc = 0;
+  for (int64_t i = 0; i < n; i++) {
+    TORCH_CHECK(params[i].is_cuda() && params[i].device() == dev &&
+                grads[i].device() == dev && exp_avgs[i].device() == dev &&
+                exp_avg_sqs[i].device() == dev && steps[i].device() == dev,
+                "all tensors must be on the same device");
+    TORCH_CHECK(params[i].is_contiguous() && grads[i].is_contiguous() &&
+                exp_avgs[i].is_contiguous() && exp_avg_sqs[i].is_contiguous());
+    TORCH_CHECK(params[i].scalar_type() == at::kBFloat16 &&
+                grads[i].scalar_type() == at::kBFloat16,
+                "params and grads must be bf16");
+    TORCH_CHECK(exp_avgs[i].scalar_type() == at::kFloat &&
+                exp_avg_sqs[i].scalar_type() == at::kFloat, "states must be fp32");
+    const int64_t ne = params[i].numel();
+    TORCH_CHECK(grads[i].numel() == ne && exp_avgs[i].numel() == ne &&
+                exp_avg_sqs[i].numel() == ne, "size mismatch");
+    TORCH_CHECK(steps[i].scalar_type() == at::kInt && steps[i].numel() == 1,
+                "step must be a 1-element int32 device tensor");
+    h[i] = (int64_t)params[i].data_ptr();
+    h[n + i] = (int64_t)grads[i].data_ptr();
+    h[2 * n + i] = (int64_t)exp_avgs[i].data_ptr();
+    h[3 * n + i] = (int64_t)exp_avg_sqs[i].data_ptr();
+    h[4 * n + i] = ne;
+    h[5 * n + i] = (int64_t)steps[i].data_ptr();
+    gprefix[i] = acc;
+    acc += (ne + kQBlock - 1) / kQBlock;
+  }
+  gprefix[n] = acc;
+  std::vector<int64_t> group_blocks(ng, 0);
+  {
+    int64_t first = 0, w = 0;
+    for (int64_t g = 0; g < ng; g++) {
+      TORCH_CHECK(group_sizes[g] >= 0 && first + group_sizes[g] <= n);
+      for (int64_t i = 0; i <= group_sizes[g]; i++)
+        uprefix[w + i] = gprefix[first + i] - gprefix[first];
+      group_blocks[g] = gprefix[first + group_sizes[g]] - gprefix[first];
+      w += group_sizes[g] + 1;
+      first += group_sizes[g];
+    }
+    TORCH_CHECK(first == n, "group_sizes must cover every tensor");
+  }
+  at::Tensor table = host.to(dev, /*non_blocking=*/true);
+  const int64_t* d = table.data_ptr<int64_t>();
+  auto stream = (tft_stream)at::cuda::getCurrentCUDAStream().stream();
+
+  const int64_t grid = std::min(acc, max_blocks);
+  auto partials = at::empty({grid}, stats.options());
+  tft::launch_grad_sumsq_partial(0, d + n, d + 4 * n, d + 6 * n, (int)n, acc,
+                                 (int)grid, partials.data_ptr<float>(), stream);
+  tft::launch_grad_sumsq_finalize(partials.data_ptr<float>(), (int)grid,
+                                  stats.data_ptr<float>(), stream);
+  if (!norm_reduce.is_none()) norm_reduce(stats.narrow(0, 0, 1));
+
+  int64_t first = 0, w = 0;
+  for (int64_t g = 0; g < ng; g++) {
+    const int64_t cnt = group_sizes[g];
+    if (cnt > 0)
+      tft::launch_adamw_clip(d + first, d + n + first, d + 2 * n + first,
+                             d + 3 * n + first, d + 4 * n + first,
+                             d + 7 * n + 1 + w, d + 5 * n + first, (int)cnt,
+                             group_blocks[g], (float)lrs[g], (float)beta1s[g],
+                             (float)beta2s[g], (float)epss[g],
+                             (float)weight_decays[g], stats.data_ptr<float>(),
+                             (float)max_norm, stream);
+    w += cnt + 1;
+    first += cnt;
+  }
+  tft::launch_adamw_bump_steps(d + 5 * n, (int)n, stats.data_ptr<float>(),
+                               skipped.data_ptr<int>(), norm_out.data_ptr<float>(),
+                               stream);
+}
+
 // ---- flash attention backward (appended) -----------------------------------
 
 // true when a logical [B,H,S,D] tensor is a transpose view of contiguous
@@ -420,6 +656,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_glu_bwd", &swiglu_glu_bwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("adamw_step", &adamw_step);
+  m.def("adamw_clip_step", &adamw_clip_step,
+        "FusedAdamW step with fused global-norm clip and non-finite skip");
+  m.def("grad_sumsq", &grad_sumsq,
+        "global sum of squares of a tensor list: 1-element fp32 device tensor");
+  m.def("clip_grad_norm", &clip_grad_norm,
+        "in-place global-norm clip; returns the pre-clip sum of squares");
   m.def("fa_fwd", &fa_fwd);
   m.def("fa_delta", &fa_delta);
   m.def("fa_bwd", &fa_bwd,

@@ -36,6 +36,14 @@ __device__ inline int find_tensor_a(const int64_t* block_prefix, int n, int64_t 
   return lo;
 }
 
+// kClip = false is the plain step: bias corrections come from the host and
+// stats/max_norm/step_ptrs are unused (null). kClip = true is the clip mode:
+// stats[0] holds the global sum of squared gradients (grad_norm.hip), the
+// clip coefficient is folded into the gradient read, a non-finite norm
+// leaves p/m/v untouched, and the bias corrections come from the per-tensor
+// device step counts (bumped afterwards by adamw_bump_steps_kernel), so a
+// skipped step costs no host sync and no bias-correction step.
+template <bool kClip>
 __global__ void adamw_kernel(const int64_t* __restrict__ param_ptrs,
                              const int64_t* __restrict__ grad_ptrs,
                              const int64_t* __restrict__ m_ptrs,
@@ -43,12 +51,25 @@ __global__ void adamw_kernel(const int64_t* __restrict__ param_ptrs,
                              const int64_t* __restrict__ numels,
                              const int64_t* __restrict__ block_prefix,
                              int n_tensors, float lr, float beta1, float beta2,
-                             float eps, float weight_decay, float bc1, float bc2) {
+                             float eps, float weight_decay, float bc1, float bc2,
+                             const float* __restrict__ stats, float max_norm,
+                             const int64_t* __restrict__ step_ptrs) {
+  float coef = 1.f;
+  if constexpr (kClip) {
+    const float norm = sqrtf(stats[0]);
+    if (!isfinite(norm)) return;  // skipped step: no store at all
+    coef = fminf(1.f, max_norm / (norm + 1e-6f));  // torch's definition
+  }
   const int64_t b = blockIdx.x;
   const int t = find_tensor_a(block_prefix, n_tensors, b);
   const int64_t off = (b - block_prefix[t]) * ABLOCK + threadIdx.x * AEPT;
   const int64_t numel = numels[t];
   if (off >= numel) return;
+  if constexpr (kClip) {
+    const float s = (float)(*reinterpret_cast<const int32_t*>(step_ptrs[t]) + 1);
+    bc1 = 1.f - powf(beta1, s);
+    bc2 = 1.f - powf(beta2, s);
+  }
 
   bf16* p = reinterpret_cast<bf16*>(param_ptrs[t]) + off;
   const bf16* g = reinterpret_cast<const bf16*>(grad_ptrs[t]) + off;
@@ -85,6 +106,19 @@ __global__ void adamw_kernel(const int64_t* __restrict__ param_ptrs,
       gv[i] = __bfloat162float(g[i]);
       mv[i] = m[i];
       vv[i] = v[i];
+    }
+  }
+
+  if constexpr (kClip) {
+    // Scale once, then hide the product from the optimizer: the update below
+    // must see an opaque value, as the plain kernel sees its loaded gradient,
+    // so that both instantiations get the same fma contraction and a
+    // coefficient of exactly 1.0 reproduces the plain kernel's moments bit for
+    // bit (tests/test_grad_clip_gpu.py holds them to that).
+#pragma unroll
+    for (int i = 0; i < AEPT; i++) {
+      if (full || i < cnt) gv[i] *= coef;
+      asm volatile("" : "+v"(gv[i]));
     }
   }
 
@@ -126,10 +160,52 @@ void launch_adamw(const int64_t* param_ptrs, const int64_t* grad_ptrs,
                   float beta2, float eps, float weight_decay,
                   float bias_correction1, float bias_correction2,
                   hipStream_t stream) {
-  hipLaunchKernelGGL(adamw_kernel, dim3((uint32_t)total_blocks), dim3(ATHREADS), 0,
-                     stream, param_ptrs, grad_ptrs, m_ptrs, v_ptrs, numels,
-                     block_prefix, n_tensors, lr, beta1, beta2, eps, weight_decay,
-                     bias_correction1, bias_correction2);
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3((uint32_t)total_blocks),
+                     dim3(ATHREADS), 0, stream, param_ptrs, grad_ptrs, m_ptrs, v_ptrs,
+                     numels, block_prefix, n_tensors, lr, beta1, beta2, eps,
+                     weight_decay, bias_correction1, bias_correction2,
+                     (const float*)nullptr, 0.f, (const int64_t*)nullptr);
+}
+
+// One thread per participating tensor, after every group's update on the same
+// stream: a finite norm advances each device step count, a non-finite one
+// advances the skipped counter instead. Thread 0 also publishes the norm.
+__global__ void adamw_bump_steps_kernel(const int64_t* __restrict__ step_ptrs,
+                                        int n_tensors,
+                                        const float* __restrict__ stats,
+                                        int32_t* __restrict__ skipped,
+                                        float* __restrict__ norm_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const float norm = sqrtf(stats[0]);
+  if (i == 0) norm_out[0] = norm;
+  if (isfinite(norm)) {
+    if (i < n_tensors) *reinterpret_cast<int32_t*>(step_ptrs[i]) += 1;
+  } else if (i == 0) {
+    skipped[0] += 1;
+  }
+}
+
+void launch_adamw_clip(const int64_t* param_ptrs, const int64_t* grad_ptrs,
+                       const int64_t* m_ptrs, const int64_t* v_ptrs,
+                       const int64_t* numels, const int64_t* block_prefix,
+                       const int64_t* step_ptrs, int n_tensors,
+                       int64_t total_blocks, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, const float* stats,
+                       float max_norm, hipStream_t stream) {
+  if (total_blocks <= 0) return;
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3((uint32_t)total_blocks),
+                     dim3(ATHREADS), 0, stream, param_ptrs, grad_ptrs, m_ptrs, v_ptrs,
+                     numels, block_prefix, n_tensors, lr, beta1, beta2, eps,
+                     weight_decay, 1.f, 1.f, stats, max_norm, step_ptrs);
+}
+
+void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,
+                             const float* stats, int32_t* skipped, float* norm_out,
+                             hipStream_t stream) {
+  if (n_tensors <= 0) return;
+  hipLaunchKernelGGL(adamw_bump_steps_kernel, dim3((n_tensors + 255) / 256),
+                     dim3(256), 0, stream, step_ptrs, n_tensors, stats, skipped,
+                     norm_out);
 }
 
 }  // namespace torchft_amd

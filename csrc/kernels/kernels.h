@@ -55,6 +55,36 @@ void launch_adamw(const int64_t* param_ptrs, const int64_t* grad_ptrs,
                   float beta2, float eps, float weight_decay,
                   float bias_correction1, float bias_correction2,
                   tft_stream stream);
+// clip mode: coefficient from stats[0] (global sum of squared gradients),
+// bias corrections from the per-tensor device int32 step counts; a
+// non-finite norm stores nothing
+void launch_adamw_clip(const int64_t* param_ptrs, const int64_t* grad_ptrs,
+                       const int64_t* m_ptrs, const int64_t* v_ptrs,
+                       const int64_t* numels, const int64_t* block_prefix,
+                       const int64_t* step_ptrs, int n_tensors,
+                       int64_t total_blocks, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, const float* stats,
+                       float max_norm, tft_stream stream);
+// finite norm: ++*step[t] for every tensor; else ++*skipped. norm_out[0] = norm
+void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,
+                             const float* stats, int32_t* skipped, float* norm_out,
+                             tft_stream stream);
+
+// grad_norm.hip ------------------------------------------------------------
+// dtype_code as above. `grid` workgroups grid-stride over total_blocks logical
+// blocks and write partials[0..grid); finalize sums n_partials of them in
+// double into stats[0] (the sum of squares, fp32).
+void launch_grad_sumsq_partial(int dtype_code, const int64_t* ptrs,
+                               const int64_t* numels, const int64_t* block_prefix,
+                               int n_tensors, int64_t total_blocks, int grid,
+                               float* partials, tft_stream stream);
+void launch_grad_sumsq_finalize(const float* partials, int n_partials, float* stats,
+                                tft_stream stream);
+// in place g *= min(1, max_norm / (sqrt(stats[0]) + 1e-6)); no-op if non-finite
+void launch_grad_scale(int dtype_code, const int64_t* ptrs, const int64_t* numels,
+                       const int64_t* block_prefix, int n_tensors,
+                       int64_t total_blocks, const float* stats, float max_norm,
+                       tft_stream stream);
 
 }  // namespace torchft_amd
 

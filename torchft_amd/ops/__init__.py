@@ -1,4 +1,5 @@
-"""CDNA4 fused ops: RMSNorm, RoPE, SwiGLU, fused AdamW.
+"""CDNA4 fused ops: RMSNorm, RoPE, SwiGLU, fused AdamW (with optional fused
+global-norm clipping), gradient norm / clip.
 
 On a HIP device these route through the in-tree gfx950 extension
 (``torchft_amd/_hip_kernels.so``, sources in ``csrc/kernels/``) and FAIL
@@ -10,7 +11,7 @@ reference implementations (used by the numerics tests as ground truth).
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import torch
 
@@ -210,12 +211,115 @@ def _local_view(t: torch.Tensor) -> torch.Tensor:
     return t.to_local() if isinstance(t, DTensor) else t
 
 
+_GRAD_NORM_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+
+
+def _sumsq_torch(tensors: List[torch.Tensor]) -> torch.Tensor:
+    """Plain-torch sum of squares (double accumulation) as fp32 [1]."""
+    total = torch.zeros((), dtype=torch.float64, device=tensors[0].device)
+    for t in tensors:
+        total = total + t.detach().double().pow(2).sum()
+    return total.float().reshape(1)
+
+
+def _as_grads(tensors_or_params) -> List[torch.Tensor]:
+    """Gradients to measure: a tensor that requires grad is a parameter and
+    contributes its ``.grad`` (skipped if None); any other tensor is taken as
+    a gradient itself. DTensors contribute their local shard."""
+    if isinstance(tensors_or_params, torch.Tensor):
+        tensors_or_params = [tensors_or_params]
+    out = []
+    for t in tensors_or_params:
+        if t.requires_grad:
+            t = t.grad
+            if t is None:
+                continue
+        t = _local_view(t)
+        if t.numel() > 0:
+            out.append(t)
+    return out
+
+
+def _use_hip_norm(grads: List[torch.Tensor]) -> bool:
+    if not grads[0].is_cuda:
+        return False
+    for g in grads:
+        if g.dtype not in _GRAD_NORM_DTYPES:
+            raise TypeError(f"grad norm kernel: unsupported dtype {g.dtype}")
+    return True
+
+
+def grad_norm(tensors_or_params, *, norm_reduce=None, max_blocks: int = 2048) -> torch.Tensor:
+    """Global L2 norm of a list of gradients (or of the ``.grad`` of a list of
+    parameters) as a 0-dim fp32 tensor on their device; no host sync.
+
+    On a HIP device: csrc/kernels/grad_norm.hip, two launches and no atomics,
+    so the value is bitwise reproducible for a given ``max_blocks`` (the cap
+    on the reduction grid). ``norm_reduce``, if given, is called with the
+    1-element fp32 sum of squares before the square root — sharded callers
+    all-reduce (SUM) it there. On CPU: plain torch.
+    """
+    grads = _as_grads(tensors_or_params)
+    if not grads:
+        raise ValueError("grad_norm: no gradients")
+    if _use_hip_norm(grads):
+        sumsq = hip_ext().grad_sumsq(grads, max_blocks)
+    else:
+        sumsq = _sumsq_torch(grads)
+    if norm_reduce is not None:
+        norm_reduce(sumsq)
+    return sumsq.sqrt().reshape(())
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm: float, *, norm_reduce=None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` for users of other optimizers:
+    scales every ``.grad`` in place by ``min(1, max_norm / (norm + 1e-6))``
+    and returns the pre-clip global norm as a 0-dim fp32 device tensor.
+    Gradients are left untouched when the norm is non-finite, and nothing
+    waits on the host. ``norm_reduce`` as in :func:`grad_norm`.
+    """
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [_local_view(p.grad) for p in parameters if p.grad is not None]
+    grads = [g for g in grads if g.numel() > 0]
+    if not grads:
+        raise ValueError("clip_grad_norm_: no gradients")
+    max_norm = float(max_norm)
+    if not max_norm > 0:
+        raise ValueError(f"max_norm must be > 0, got {max_norm}")
+    if _use_hip_norm(grads):
+        sumsq = hip_ext().clip_grad_norm(grads, max_norm, 2048, norm_reduce)
+        return sumsq.sqrt().reshape(())
+    sumsq = _sumsq_torch(grads)
+    if norm_reduce is not None:
+        norm_reduce(sumsq)
+    norm = sumsq.sqrt().reshape(())
+    coef = (max_norm / (norm + 1e-6)).clamp(max=1.0)
+    coef = torch.where(torch.isfinite(norm), coef, torch.ones_like(coef))
+    for g in grads:
+        g.mul_(coef)
+    return norm
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """Single-kernel multi-tensor AdamW for bf16 params (fp32 moments).
 
     One launch per step updates every parameter (csrc/kernels/fused_adamw.hip);
     falls back to torch's foreach AdamW path on CPU. DTensor params (the
     FSDP2 sharded path) are updated on their local shards.
+
+    ``max_grad_norm`` (opt-in; ``math.inf`` allowed) turns on the clip mode:
+    the global L2 norm over all param groups is reduced on the device
+    (csrc/kernels/grad_norm.hip), the clip coefficient is folded into the
+    update's gradient read, and a non-finite norm skips the step on the
+    device — ``p``, ``exp_avg``, ``exp_avg_sq`` and the bias-correction step
+    stay untouched, with no host sync. In this mode ``state[p]["step"]`` is a
+    0-dim int32 device tensor, ``last_grad_norm`` holds the pre-clip norm of
+    the last step (non-finite if it was skipped) and ``skipped_steps`` counts
+    the skips, both as device tensors. ``norm_reduce``, if given, is called
+    with the 1-element fp32 sum of squares before the update; FSDP2/DTensor
+    callers all-reduce (SUM) their shard's value there.
     """
 
     def __init__(
@@ -225,13 +329,137 @@ class FusedAdamW(torch.optim.Optimizer):
         betas=(0.9, 0.95),
         eps: float = 1e-8,
         weight_decay: float = 0.01,
+        max_grad_norm: Optional[float] = None,
+        norm_reduce: Optional[Callable[[torch.Tensor], None]] = None,
     ) -> None:
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0:
+                raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm}")
+        elif norm_reduce is not None:
+            raise ValueError("norm_reduce needs max_grad_norm (math.inf to only report)")
+        self.max_grad_norm = max_grad_norm
+        self.norm_reduce = norm_reduce
+        self.last_grad_norm: Optional[torch.Tensor] = None
+        self.skipped_steps: Optional[torch.Tensor] = None
+        if max_grad_norm is not None:
+            dev = _local_view(self.param_groups[0]["params"][0]).device
+            self._clip_buffers(dev)
+
+    def _clip_buffers(self, dev: torch.device) -> None:
+        skipped = self.skipped_steps
+        self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        self.skipped_steps = torch.zeros((), dtype=torch.int32, device=dev)
+        if skipped is not None:  # params moved since construction
+            self.skipped_steps.copy_(skipped)
+
+    def load_state_dict(self, state_dict) -> None:  # noqa: D102
+        # torch leaves a "step" entry as it was saved (an int or a tensor on
+        # any device); make it what this optimizer's mode steps with.
+        super().load_state_dict(state_dict)
+        for p, state in self.state.items():
+            if "step" not in state:
+                continue
+            step = state["step"]
+            if self.max_grad_norm is not None:
+                dev = _local_view(p).device
+                state["step"] = torch.as_tensor(step).to(
+                    device=dev, dtype=torch.int32).reshape(()).clone()
+            elif isinstance(step, torch.Tensor):
+                state["step"] = int(step.item())
+
+    @torch.no_grad()
+    def _step_clip(self) -> None:
+        params: List[torch.Tensor] = []
+        grads: List[torch.Tensor] = []
+        exp_avgs: List[torch.Tensor] = []
+        exp_avg_sqs: List[torch.Tensor] = []
+        steps: List[torch.Tensor] = []
+        groups = []
+        for group in self.param_groups:
+            n0 = len(params)
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                state = self.state[p]
+                p_loc = _local_view(p)
+                if len(state) == 0:
+                    # the step lives on the device: a skipped step must not
+                    # advance it, and the host never learns which were skipped
+                    state["step"] = torch.zeros((), dtype=torch.int32, device=p_loc.device)
+                    state["exp_avg"] = torch.zeros_like(p_loc, dtype=torch.float32)
+                    state["exp_avg_sq"] = torch.zeros_like(p_loc, dtype=torch.float32)
+                params.append(p_loc)
+                grads.append(_local_view(p.grad))
+                exp_avgs.append(state["exp_avg"])
+                exp_avg_sqs.append(state["exp_avg_sq"])
+                steps.append(state["step"])
+            groups.append((group, len(params) - n0))
+        if not params:
+            return
+        dev = params[0].device
+        if self._sumsq.device != dev:
+            self._clip_buffers(dev)
+
+        if dev.type == "cuda" and all(
+            p.dtype == torch.bfloat16 and g.dtype == torch.bfloat16
+            for p, g in zip(params, grads)
+        ):
+            # norm over everything, then one update launch per param group —
+            # no bucketing by step count, the kernel reads each tensor's own
+            hip_ext().adamw_clip_step(
+                params, grads, exp_avgs, exp_avg_sqs, steps,
+                [cnt for _, cnt in groups],
+                [float(g["lr"]) for g, _ in groups],
+                [float(g["betas"][0]) for g, _ in groups],
+                [float(g["betas"][1]) for g, _ in groups],
+                [float(g["eps"]) for g, _ in groups],
+                [float(g["weight_decay"]) for g, _ in groups],
+                self.max_grad_norm, 2048, self._sumsq, self.skipped_steps,
+                self.last_grad_norm, self.norm_reduce,
+            )
+            return
+
+        # plain-torch path, same semantics and still no host sync: every
+        # tensor is rewritten through where(finite, new, old)
+        self._sumsq.copy_(_sumsq_torch(grads))
+        if self.norm_reduce is not None:
+            self.norm_reduce(self._sumsq)
+        norm = self._sumsq.sqrt().reshape(())
+        finite = torch.isfinite(norm)
+        coef = (self.max_grad_norm / (norm + 1e-6)).clamp(max=1.0)
+        i = 0
+        for group, cnt in groups:
+            beta1, beta2 = group["betas"]
+            for p, g, m, v, s in zip(params[i:i + cnt], grads[i:i + cnt],
+                                     exp_avgs[i:i + cnt], exp_avg_sqs[i:i + cnt],
+                                     steps[i:i + cnt]):
+                gf = g.float() * coef
+                s1 = (s + 1).double()
+                bc1 = (1 - beta1 ** s1).float()
+                bc2 = (1 - beta2 ** s1).float()
+                m_new = m * beta1 + gf * (1 - beta1)
+                v_new = v * beta2 + gf * gf * (1 - beta2)
+                denom = (v_new / bc2).sqrt_().add_(group["eps"])
+                update = (m_new / bc1) / denom + group["weight_decay"] * p.float()
+                p_new = p + (-group["lr"] * update).to(p.dtype)
+                p.copy_(torch.where(finite, p_new, p))
+                m.copy_(torch.where(finite, m_new, m))
+                v.copy_(torch.where(finite, v_new, v))
+                s.add_(finite.to(s.dtype))
+            i += cnt
+        self.last_grad_norm.copy_(norm)
+        self.skipped_steps.add_((~finite).to(torch.int32))
 
     @torch.no_grad()
     def step(self, closure=None):  # noqa: D102
         assert closure is None
+        if self.max_grad_norm is not None:
+            self._step_clip()
+            return None
         for group in self.param_groups:
             # Params that intermittently have grad=None (e.g. unused-param
             # DDP) accumulate different step counts; the bias correction is
