@@ -1,5 +1,5 @@
 // torch-extension bindings for the CDNA4 kernels (fp8 quantized-collective
-// trio, fused model ops, fused AdamW). Tensor-level API consumed by
+// trio, fused model ops, fused AdamW, DiLoCo outer sync). Tensor-level API consumed by
 // torchft_amd.ops / torchft_amd.quantization.
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
@@ -502,6 +502,108 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
                                stream);
 }
 
+// ---- fused DiLoCo outer sync ---------------------------------------------------
+
+namespace {
+
+// One pinned table for `lists.size()` parallel tensor lists of one dtype:
+// [ptrs of list 0 | ... | ptrs of list k-1 | numels | block_prefix (n+1)],
+// with zero-numel tensors left out. Copied to the device once.
+struct SyncTable {
+  at::Tensor dev;
+  int64_t n = 0;       // tensors kept
+  int64_t blocks = 0;  // logical 2048-element blocks
+  int code = 0;        // dtype_code of kernels.h
+};
+
+SyncTable build_sync_table(const std::vector<const std::vector<at::Tensor>*>& lists,
+                           const char* what) {
+  const int64_t k = (int64_t)lists.size();
+  const auto& first = *lists[0];
+  const int64_t n_all = (int64_t)first.size();
+  TORCH_CHECK(n_all > 0, what, ": need at least one tensor");
+  const auto dev = first[0].device();
+  const auto st = first[0].scalar_type();
+  SyncTable tb;
+  tb.code = st == at::kBFloat16 ? 0 : st == at::kHalf ? 1 : st == at::kFloat ? 2 : -1;
+  TORCH_CHECK(tb.code >= 0, what, ": unsupported dtype ", st);
+  std::vector<int64_t> keep;
+  for (int64_t i = 0; i < n_all; i++) {
+    for (int64_t j = 0; j < k; j++) {
+      TORCH_CHECK((int64_t)lists[j]->size() == n_all, what, ": list lengths differ");
+      const auto& t = (*lists[j])[i];
+      TORCH_CHECK(t.is_cuda() && t.device() == dev, what,
+                  ": all tensors must be on one device");
+      TORCH_CHECK(t.scalar_type() == st, what, ": mixed dtypes (", st, " and ",
+                  t.scalar_type(), ")");
+      TORCH_CHECK(t.is_contiguous(), what, ": tensors must be contiguous");
+      TORCH_CHECK(t.numel() == first[i].numel(), what, ": size mismatch at tensor ", i);
+    }
+    if (first[i].numel() > 0) keep.push_back(i);
+  }
+  tb.n = (int64_t)keep.size();
+  if (tb.n == 0) return tb;
+  const int64_t n = tb.n;
+  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
+  at::Tensor host = at::empty({(k + 2) * n + 1}, opts);
+  int64_t* h = host.data_ptr<int64_t>();
+  int64_t* numels = h + k * n;
+  int64_t* prefix = h + (k + 1) * n;
+  int64_t acc = 0;
+  for (int64_t i = 0; i < n; i++) {
+    for (int64_t j = 0; j < k; j++) h[j * n + i] = (int64_t)(*lists[j])[keep[i]].data_ptr();
+    numels[i] = first[keep[i]].numel();
+    prefix[i] = acc;
+    acc += (numels[i] + kQBlock - 1) / kQBlock;
+  }
+  prefix[n] = acc;
+  TORCH_CHECK(acc < (int64_t(1) << 31), what, ": too many elements for one launch");
+  tb.blocks = acc;
+  tb.dev = host.to(dev, /*non_blocking=*/true);
+  return tb;
+}
+
+}  // namespace
+
+// outs[i] = minuends[i] - subtrahends[i], one launch for the whole list
+void diloco_pseudograd(const std::vector<at::Tensor>& outs,
+                       const std::vector<at::Tensor>& minuends,
+                       const std::vector<at::Tensor>& subtrahends) {
+  auto tb = build_sync_table({&outs, &minuends, &subtrahends}, "pseudograd_");
+  if (tb.n == 0) return;
+  const int64_t n = tb.n;
+  const int64_t* d = tb.dev.data_ptr<int64_t>();
+  auto stream = (tft_stream)at::cuda::getCurrentCUDAStream().stream();
+  tft::launch_pseudograd(tb.code, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, (int)n,
+                         tb.blocks, stream);
+}
+
+// Outer SGD step + re-snapshot + lerp for one param group; momentum_bufs is
+// empty when momentum == 0.
+void diloco_outer_step(const std::vector<at::Tensor>& snapshots,
+                       const std::vector<at::Tensor>& params,
+                       const std::vector<at::Tensor>& pseudograds,
+                       const std::vector<at::Tensor>& momentum_bufs, double lr,
+                       double momentum, bool nesterov, double alpha) {
+  const bool has_m = momentum != 0.0;
+  TORCH_CHECK(has_m == !momentum_bufs.empty(),
+              "diloco_outer_step_: momentum buffers are needed exactly when "
+              "momentum != 0");
+  TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "alpha must be in [0, 1], got ", alpha);
+  std::vector<const std::vector<at::Tensor>*> lists = {&snapshots, &params, &pseudograds};
+  if (has_m) lists.push_back(&momentum_bufs);
+  auto tb = build_sync_table(lists, "diloco_outer_step_");
+  if (tb.n == 0) return;
+  const int64_t n = tb.n;
+  const int64_t k = (int64_t)lists.size();
+  const int64_t* d = tb.dev.data_ptr<int64_t>();
+  auto stream = (tft_stream)at::cuda::getCurrentCUDAStream().stream();
+  tft::launch_outer_sgd(tb.code, has_m, d, d + n, d + 2 * n,
+                        has_m ? d + 3 * n : nullptr, d + k * n, d + (k + 1) * n, (int)n,
+                        tb.blocks, (float)lr, (float)momentum, nesterov, (float)alpha,
+                        stream);
+}
+
 // ---- flash attention backward (appended) -----------------------------------
 
 // true when a logical [B,H,S,D] tensor is a transpose view of contiguous
@@ -662,6 +764,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "global sum of squares of a tensor list: 1-element fp32 device tensor");
   m.def("clip_grad_norm", &clip_grad_norm,
         "in-place global-norm clip; returns the pre-clip sum of squares");
+  m.def("diloco_pseudograd", &diloco_pseudograd,
+        "multi-tensor outs[i] = minuends[i] - subtrahends[i]");
+  m.def("diloco_outer_step", &diloco_outer_step,
+        "fused DiLoCo outer SGD step, re-snapshot and local-progress lerp");
   m.def("fa_fwd", &fa_fwd);
   m.def("fa_delta", &fa_delta);
   m.def("fa_bwd", &fa_bwd,

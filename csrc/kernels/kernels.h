@@ -109,6 +109,22 @@ void launch_cross_entropy(void* logits, const int64_t* targets, float* row_loss,
                           int64_t ignore_index, float z_loss, bool write_grad,
                           tft_stream stream);
 
+// diloco_sync.hip -----------------------------------------------------------
+// dtype_code as above; every tensor of one call has that dtype.
+// out[t] = a[t] - b[t], one rounding
+void launch_pseudograd(int dtype_code, const int64_t* out_ptrs, const int64_t* a_ptrs,
+                       const int64_t* b_ptrs, const int64_t* numels,
+                       const int64_t* block_prefix, int n_tensors,
+                       int64_t total_blocks, tft_stream stream);
+// outer SGD on the snapshots g from the pseudo-gradients d (momentum buffers m
+// read only when has_momentum), then l <- lerp(new g, l, alpha); g, m, l in place
+void launch_outer_sgd(int dtype_code, bool has_momentum, const int64_t* g_ptrs,
+                      const int64_t* l_ptrs, const int64_t* d_ptrs,
+                      const int64_t* m_ptrs, const int64_t* numels,
+                      const int64_t* block_prefix, int n_tensors,
+                      int64_t total_blocks, float lr, float mu, bool nesterov,
+                      float alpha, tft_stream stream);
+
 // mfma_probe.hip ------------------------------------------------------------
 void launch_mfma_probe(const void* A, const void* B, float* D, tft_stream s);
 

@@ -32,6 +32,10 @@ def main() -> None:
     p.add_argument("--fragments", type=int, default=2)
     p.add_argument("--quantize", action="store_true",
                    help="fp8-quantized outer allreduce (CDNA4 kernels)")
+    p.add_argument("--fused-sync", action="store_true",
+                   help="fused outer sync: device-resident snapshot, one "
+                        "pseudo-gradient launch and one outer-step launch per "
+                        "fragment (needs the SGD outer optimizer used here)")
     args = p.parse_args()
 
     replica_group_id = int(os.environ.get("REPLICA_GROUP_ID", "0"))
@@ -82,6 +86,7 @@ def main() -> None:
         sync_every=args.sync_every,
         fragment_sync_delay=args.fragment_sync_delay,
         should_quantize=args.quantize,
+        fused_sync=args.fused_sync,
     )
 
     with diloco:

@@ -26,7 +26,9 @@ trajectory — but the implementation is organized differently:
 MI355X notes: the outer allreduce can take the fp8-quantized path
 (``should_quantize=True`` -> CDNA4 kernels + alltoall/allgather across all
 7 xGMI links); backups stage to pinned host memory by default, and the
-1 GiB default bucket is sized to saturate a per-link xGMI ring.
+1 GiB default bucket is sized to saturate a per-link xGMI ring. With
+``DiLoCo(fused_sync=True)`` the backups live in HBM instead and the outer sync
+runs through two multi-tensor HIP kernels (csrc/kernels/diloco_sync.hip).
 """
 
 from __future__ import annotations
@@ -230,11 +232,15 @@ class _BucketPlan:
     ``cap_bytes``. Each bucket owns its slot table, so scatter-back is bound
     per bucket by construction."""
 
-    def __init__(self, tensors: List[torch.Tensor], cap_bytes: int) -> None:
+    def __init__(
+        self, tensors: List[torch.Tensor], cap_bytes: int, align_bytes: int = 1
+    ) -> None:
         assert tensors, "no tensors to pack"
         self.dtype = tensors[0].dtype
         self.device = tensors[0].device
         cap_elems = max(1, cap_bytes // tensors[0].element_size())
+        # slot offsets are rounded up to this many elements (1: packed tight)
+        align = max(1, align_bytes // tensors[0].element_size())
         for t in tensors:
             if t.numel() > cap_elems:
                 raise ValueError(
@@ -246,6 +252,7 @@ class _BucketPlan:
         used = 0
         for t in tensors:
             n = t.numel()
+            used = -(-used // align) * align
             if used + n > cap_elems and current:
                 self.buckets.append(current)
                 current, used = [], 0
@@ -253,6 +260,16 @@ class _BucketPlan:
             used += n
         if current:
             self.buckets.append(current)
+
+    def allocate(self, slots: List[_BucketSlot]) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """A zeroed flat bucket and one view per slot, shaped like its tensor.
+        Alignment padding stays zero, so it is inert in an allreduce."""
+        size = slots[-1].offset + slots[-1].numel
+        flat = torch.zeros(size, dtype=self.dtype, device=self.device)
+        views = [
+            flat[s.offset : s.offset + s.numel].view_as(s.tensor) for s in slots
+        ]
+        return flat, views
 
     def flatten(self, slots: List[_BucketSlot]) -> torch.Tensor:
         size = slots[-1].offset + slots[-1].numel
@@ -286,6 +303,16 @@ class _StreamingDiLoCoFragment:
                       outer-step on the averaged pseudo-grads, re-snapshot,
                       and lerp local progress back in by
                       ``fragment_update_alpha``.
+
+    With ``fused_sync=True`` the snapshot lives on the parameters' device,
+    ``stage()`` is one multi-tensor launch writing the pseudo-gradients into
+    flat zeroed buckets (one allreduce each, split by ``bucket_cap_mb``) and
+    the committed outer step is one launch per param group
+    (``ops.pseudograd_`` / ``ops.diloco_outer_step_``). The outer optimizer
+    must be a plain ``torch.optim.SGD``; its ``lr``/``momentum``/``nesterov``
+    are read from ``param_groups`` at every outer step and its own
+    ``momentum_buffer`` state is updated in place, but ``step()`` itself is
+    never called, so step hooks registered on it do not fire.
     """
 
     bucket_cap_mb: int = 1 * 1024 * 1024 * 1024
@@ -307,10 +334,21 @@ class _StreamingDiLoCoFragment:
         should_quantize: bool = False,
         fragment_sync_delay: int = 0,
         fragment_update_alpha: float = 0.0,
+        fused_sync: bool = False,
     ) -> None:
         if fragment_sync_offset > sync_every:
             raise ValueError("Fragment must be synced once before `sync_every` steps")
         assert sync_every >= 1
+
+        self._fused_sync = fused_sync
+        if fused_sync:
+            backup_device = self._check_fused(
+                model_fragment, outer_optimizer, backup_device
+            )
+            pin_memory = False
+        # fused mode: (flat bucket, per-parameter views) of the sync in flight
+        self._fused_buckets: List[Tuple[torch.Tensor, List[torch.Tensor]]] = []
+        self._fused_plan: Optional[_BucketPlan] = None
 
         self._manager = manager
         self._model_fragment = model_fragment
@@ -353,6 +391,60 @@ class _StreamingDiLoCoFragment:
             if pin_memory and t.device.type == "cpu" and torch.cuda.is_available():
                 t = t.pin_memory()
             self.original_parameters[name] = t
+
+    @staticmethod
+    def _check_fused(
+        model_fragment: nn.Module,
+        outer_optimizer: optim.Optimizer,
+        backup_device: Optional[torch.device],
+    ) -> torch.device:
+        """Validate a ``fused_sync=True`` configuration; returns the device
+        the snapshot lives on (the parameters' own)."""
+        params = list(model_fragment.parameters())
+        if not params:
+            raise ValueError("fused_sync: the fragment has no parameters")
+        if DTensor is not None and any(isinstance(p, DTensor) for p in params):
+            raise NotImplementedError(
+                "fused_sync does not support DTensor (sharded) parameters"
+            )
+        device = params[0].device
+        dtypes = {p.dtype for p in params}
+        if len(dtypes) > 1:
+            raise ValueError(
+                "fused_sync needs one dtype per fragment, got mixed dtypes "
+                f"{sorted(str(d) for d in dtypes)}"
+            )
+        if any(p.device != device for p in params):
+            raise ValueError("fused_sync needs all parameters of a fragment on one device")
+        if backup_device is not None:
+            b = torch.device(backup_device)
+            same = b.type == device.type and (
+                b.index is None or device.index is None or b.index == device.index
+            )
+            if not same:
+                raise ValueError(
+                    f"fused_sync keeps the snapshot on the parameters' device "
+                    f"({device}); backup_device={b} is not supported"
+                )
+        if type(outer_optimizer) is not optim.SGD:
+            raise ValueError(
+                "fused_sync needs torch.optim.SGD as the outer optimizer, got "
+                f"{type(outer_optimizer).__name__}"
+            )
+        stepped = {id(p) for g in outer_optimizer.param_groups for p in g["params"]}
+        if any(id(p) not in stepped for p in params):
+            raise ValueError(
+                "fused_sync: every parameter of the fragment must be in the "
+                "outer optimizer's param_groups"
+            )
+        for group in outer_optimizer.param_groups:
+            for key in ("dampening", "weight_decay", "maximize"):
+                if group[key]:
+                    raise ValueError(
+                        f"fused_sync does not support {key}={group[key]!r} on "
+                        "the outer optimizer"
+                    )
+        return device
 
     # -- snapshots ----------------------------------------------------------
 
@@ -403,6 +495,9 @@ class _StreamingDiLoCoFragment:
     @torch.profiler.record_function("torchft_amd::local_sgd::prepare_sync")
     def prepare_sync(self) -> None:
         """Phase 1: pseudo-gradients + allreduce launch on the side stream."""
+        if self._fused_sync:
+            self._prepare_sync_fused()
+            return
         with torch.no_grad():
             for name, p in self._named_params():
                 local = p.to_local() if (
@@ -426,6 +521,73 @@ class _StreamingDiLoCoFragment:
                             should_quantize=self.should_quantize,
                         )
                     )
+
+    def _prepare_sync_fused(self) -> None:
+        """Phase 1, fused: one launch writes ``original - local`` for the
+        whole fragment straight into zeroed flat buckets (slots 16 B aligned),
+        then one allreduce per bucket. Nothing is flattened or scattered
+        back: the outer step reads the bucket views."""
+        from torchft_amd import ops
+
+        names = [name for name, _ in self._named_params()]
+        params = [p.data for _, p in self._named_params()]
+        if self._fused_plan is None:
+            self._fused_plan = _BucketPlan(params, self.bucket_cap_mb, align_bytes=16)
+        plan = self._fused_plan
+        assert not self._fused_buckets
+        self._fused_buckets = [plan.allocate(slots) for slots in plan.buckets]
+        views = [v for _, vs in self._fused_buckets for v in vs]
+        ops.pseudograd_(
+            views, [self.original_parameters[name] for name in names], params
+        )
+
+        assert not self._inflight
+        if self._stream is not None:
+            self._stream.wait_stream(torch.cuda.current_stream())
+        with self._side_stream():
+            for flat, _ in self._fused_buckets:
+                self._inflight.append(
+                    self._manager.allreduce(flat, should_quantize=self.should_quantize)
+                )
+
+    def _outer_step_fused(self) -> None:
+        """Phase 3, fused: per param group one launch does the SGD step on
+        the snapshot, the re-snapshot and the merge of local progress."""
+        from torchft_amd import ops
+
+        by_param = {id(p): name for name, p in self._named_params()}
+        grads = {
+            name: view
+            for (name, _), view in zip(
+                self._named_params(),
+                (v for _, vs in self._fused_buckets for v in vs),
+            )
+        }
+        opt = self._outer_optimizer
+        for group in opt.param_groups:
+            mine = [p for p in group["params"] if id(p) in by_param]
+            if not mine:
+                continue
+            momentum = float(group["momentum"])
+            bufs = None
+            if momentum != 0:
+                bufs = []
+                for p in mine:
+                    state = opt.state[p]
+                    if state.get("momentum_buffer") is None:
+                        # zeros: mu*0 + d == d, torch's clone-on-first-step
+                        state["momentum_buffer"] = torch.zeros_like(p.data)
+                    bufs.append(state["momentum_buffer"])
+            ops.diloco_outer_step_(
+                [self.original_parameters[by_param[id(p)]] for p in mine],
+                [p.data for p in mine],
+                [grads[by_param[id(p)]] for p in mine],
+                bufs,
+                lr=float(group["lr"]),
+                momentum=momentum,
+                nesterov=bool(group["nesterov"]),
+                alpha=self._fragment_update_alpha,
+            )
 
     def _side_stream(self):
         return (
@@ -471,6 +633,18 @@ class _StreamingDiLoCoFragment:
                 self._stream_fence = torch.cuda.Event()
                 self._stream_fence.record()
         self.wait()
+
+        if self._fused_sync:
+            # the kernel reads the live parameters as the local progress, so
+            # nothing is saved or restored ahead of the commit barrier
+            committed = self._manager.should_commit()
+            if committed:
+                self._outer_step_fused()
+            else:
+                self.restore_parameters()
+            self._outer_optimizer.zero_grad()
+            self._fused_buckets = []
+            return committed
 
         # keep local progress for the merge, then roll back to the globals
         with torch.no_grad():
@@ -541,6 +715,18 @@ class DiLoCo:
     one fragment stages its outer allreduce, ``fragment_sync_delay`` steps
     later it commits. Requires the Manager in synchronous-quorum mode: the
     schedule must be a pure function of the committed step on every replica.
+
+    ``fused_sync=True`` (opt-in) runs the outer sync through the fused HIP
+    kernels of ``torchft_amd.ops.diloco``: the snapshot is kept on the
+    parameters' device (``backup_device=None`` means that device, any other
+    device raises, ``pin_memory`` is ignored), the pseudo-gradients always
+    travel in flat buckets capped by ``bucket_cap_mb``, and the outer
+    optimizer must be exactly ``torch.optim.SGD`` with ``dampening == 0``,
+    ``weight_decay == 0`` and ``maximize == False`` (``momentum``, ``nesterov``
+    and an LR schedule are free). ``outer_optimizer.step()`` is not called in
+    this mode, so its step hooks do not fire; its ``momentum_buffer`` state is
+    the one updated. DTensor parameters, a CPU-resident snapshot and other
+    outer optimizers are not supported in fused mode.
     """
 
     def __init__(
@@ -557,6 +743,7 @@ class DiLoCo:
         should_quantize: bool = False,
         fragment_sync_delay: int = 0,
         fragment_update_alpha: float = 0.0,
+        fused_sync: bool = False,
     ) -> None:
         n = len(model_fragments)
         if isinstance(outer_optimizer, list) and len(outer_optimizer) != n:
@@ -602,6 +789,7 @@ class DiLoCo:
                 should_quantize,
                 fragment_sync_delay,
                 fragment_update_alpha,
+                fused_sync=fused_sync,
             )
             for i, frag in enumerate(model_fragments)
         ]

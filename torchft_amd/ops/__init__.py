@@ -1,5 +1,6 @@
 """CDNA4 fused ops: RMSNorm, RoPE, SwiGLU, fused AdamW (with optional fused
-global-norm clipping), gradient norm / clip.
+global-norm clipping), gradient norm / clip, the fused loss head and the
+fused DiLoCo outer sync (``pseudograd_``, ``diloco_outer_step_``).
 
 On a HIP device these route through the in-tree gfx950 extension
 (``torchft_amd/_hip_kernels.so``, sources in ``csrc/kernels/``) and FAIL
@@ -507,3 +508,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
 # at the bottom: cross_entropy.py imports hip_ext from this module
 from torchft_amd.ops.cross_entropy import linear_cross_entropy  # noqa: E402,F401
+
+# ----------------------------------------------------------------- DiLoCo outer sync
+
+from torchft_amd.ops.diloco import diloco_outer_step_, pseudograd_  # noqa: E402,F401
