@@ -10,12 +10,13 @@
 #include <vector>
 
 #include "kernels.h"
+#include "multi_tensor_host.h"
 
 namespace tft = torchft_amd;
 
 namespace {
 
-constexpr int64_t kQBlock = 2048;
+using TensorList = std::vector<at::Tensor>;
 
 struct PackGeom {
   int64_t total_blocks = 0;
@@ -24,50 +25,139 @@ struct PackGeom {
   int64_t slice_bytes = 0;
 };
 
-PackGeom pack_geometry(const std::vector<at::Tensor>& tensors, int64_t world) {
+PackGeom pack_geometry(const TensorList& tensors, int64_t world) {
   PackGeom g;
-  for (auto& t : tensors) g.total_blocks += (t.numel() + kQBlock - 1) / kQBlock;
+  for (auto& t : tensors) g.total_blocks += (t.numel() + tft::kMtBlock - 1) / tft::kMtBlock;
   g.padded_blocks = ((g.total_blocks + world - 1) / world) * world;
   g.blocks_per_rank = g.padded_blocks / world;
-  g.slice_bytes = g.blocks_per_rank * (4 + kQBlock);
+  g.slice_bytes = g.blocks_per_rank * (4 + tft::kMtBlock);
   return g;
 }
 
-// Builds the device-side metadata arrays (ptrs, block prefix, numels).
-struct DeviceMeta {
-  at::Tensor ptrs, prefix, numels;
+// dtype_code of kernels.h, -1 for a dtype the multi-tensor kernels do not take
+int dtype_code(at::ScalarType st) {
+  return st == at::kBFloat16 ? tft::kBF16
+         : st == at::kHalf   ? tft::kF16
+         : st == at::kFloat  ? tft::kF32
+                             : -1;
+}
+
+// One pointer column of a table to be: a tensor list and the dtype every
+// entry must have. `one_element` columns (device step counts) hold 1-element
+// tensors instead of tensors of the row's size.
+struct Column {
+  const TensorList* list;
+  at::ScalarType dtype;
+  bool one_element = false;
 };
 
-DeviceMeta build_meta(const std::vector<at::Tensor>& tensors) {
-  const int64_t n = (int64_t)tensors.size();
-  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
-  at::Tensor host = at::empty({3 * n + 1}, opts);
-  int64_t* h = host.data_ptr<int64_t>();
-  int64_t* ptrs = h;
-  int64_t* numels = h + n;
-  int64_t* prefix = h + 2 * n;  // n+1 entries
-  int64_t acc = 0;
-  for (int64_t i = 0; i < n; i++) {
-    auto& t = tensors[i];
-    TORCH_CHECK(t.is_contiguous(), "fp8 pack requires contiguous tensors");
-    TORCH_CHECK(t.is_cuda(), "fp8 pack requires device tensors");
-    ptrs[i] = (int64_t)t.data_ptr();
-    numels[i] = t.numel();
-    prefix[i] = acc;
-    acc += (t.numel() + kQBlock - 1) / kQBlock;
+// Every multi-tensor table of one binding call (kernels.h, MultiTensorTable):
+// add() validates and stages, upload() lays them out back to back in ONE
+// pinned buffer and copies it to the device once, table() hands a launcher
+// its view. The same rules hold for every user: all tensors on the device of
+// the first, the column's dtype, contiguous, the columns of a row equal in
+// size, the lists equal in length. Zero-numel rows are left out, so they
+// cost no block and an all-empty table launches nothing. Users whose kernels
+// have no element path for a tensor off a 16 B boundary (the fp8 pack) ask
+// for `need_16b_alignment`, and such a tensor is refused here.
+class TableSet {
+ public:
+  TableSet(const at::Tensor& first, const char* what, bool need_16b_alignment = false)
+      : dev_(first.device()), what_(what), need_16b_alignment_(need_16b_alignment) {
+    TORCH_CHECK(first.is_cuda(), what_, ": requires device tensors");
   }
-  prefix[n] = acc;
-  at::Tensor dev = host.to(tensors[0].device(), /*non_blocking=*/true);
-  DeviceMeta m;
-  m.ptrs = dev.narrow(0, 0, n);
-  m.numels = dev.narrow(0, n, n);
-  m.prefix = dev.narrow(0, 2 * n, n + 1);
-  return m;
+
+  // rows [first, first + count) of the parallel lists as one table
+  int add(const std::vector<Column>& cols, int64_t first, int64_t count) {
+    Staged st;
+    st.n_cols = (int)cols.size();
+    const int64_t len = (int64_t)cols[0].list->size();
+    TORCH_CHECK(first >= 0 && count >= 0 && first + count <= len, what_,
+                ": rows out of range");
+    for (auto& c : cols)
+      TORCH_CHECK((int64_t)c.list->size() == len, what_, ": list lengths differ");
+    for (int64_t i = first; i < first + count; i++) {
+      const int64_t ne = (*cols[0].list)[i].numel();
+      for (auto& c : cols) {
+        const at::Tensor& t = (*c.list)[i];
+        TORCH_CHECK(t.is_cuda() && t.device() == dev_, what_,
+                    ": all tensors must be on one device");
+        TORCH_CHECK(t.scalar_type() == c.dtype, what_, ": mixed dtypes (expected ",
+                    c.dtype, ", got ", t.scalar_type(), " at tensor ", i, ")");
+        TORCH_CHECK(t.is_contiguous(), what_, ": tensors must be contiguous");
+        TORCH_CHECK(t.numel() == (c.one_element ? 1 : ne), what_,
+                    ": size mismatch at tensor ", i);
+      }
+      if (ne == 0) continue;
+      for (auto& c : cols) {
+        const int64_t addr = (int64_t)(*c.list)[i].data_ptr();
+        TORCH_CHECK(!need_16b_alignment_ || (addr & 15) == 0, what_, ": tensor ", i,
+                    " does not start on a 16-byte boundary");
+        st.addrs.push_back(addr);
+      }
+      st.numels.push_back(ne);
+    }
+    st.offset = words_;
+    words_ += tft::mt_table_words((int64_t)st.numels.size(), st.n_cols);
+    staged_.push_back(std::move(st));
+    return (int)staged_.size() - 1;
+  }
+  int add(const std::vector<Column>& cols) {
+    return add(cols, 0, (int64_t)cols[0].list->size());
+  }
+
+  void upload() {
+    auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
+    at::Tensor host = at::empty({words_}, opts);
+    int64_t* h = host.data_ptr<int64_t>();
+    for (auto& st : staged_) {
+      st.blocks = tft::mt_write_table(h + st.offset, (int64_t)st.numels.size(), st.n_cols,
+                                      st.addrs.data(), st.numels.data());
+      TORCH_CHECK(st.blocks >= 0, what_, ": too many elements for one launch");
+    }
+    dev_words_ = host.to(dev_, /*non_blocking=*/true);
+  }
+
+  // after upload()
+  tft::MultiTensorTable table(int handle) const {
+    const Staged& st = staged_[handle];
+    return tft::mt_view(dev_words_.data_ptr<int64_t>(), st.offset,
+                        (int64_t)st.numels.size(), st.n_cols, st.blocks);
+  }
+
+ private:
+  struct Staged {
+    int n_cols = 0;
+    std::vector<int64_t> addrs;  // row by row
+    std::vector<int64_t> numels;
+    int64_t offset = 0;  // first int64 word of this table
+    int64_t blocks = 0;
+  };
+  at::Device dev_;
+  const char* what_;
+  bool need_16b_alignment_;
+  std::vector<Staged> staged_;
+  int64_t words_ = 0;
+  at::Tensor dev_words_;
+};
+
+// dtype_code of a call whose tensors all share the dtype of the first; the
+// table's checks hold the others to it
+int first_dtype_code(const TensorList& tensors, const char* what) {
+  TORCH_CHECK(!tensors.empty(), what, ": need at least one tensor");
+  const int code = dtype_code(tensors[0].scalar_type());
+  TORCH_CHECK(code >= 0, what, ": unsupported dtype ", tensors[0].scalar_type());
+  return code;
+}
+
+tft_stream current_stream() {
+  return (tft_stream)at::cuda::getCurrentCUDAStream().stream();
 }
 
 }  // namespace
 
 // ---- fp8 quantized-collective support --------------------------------------
+// table: col 0 = the tensors, all of the first one's dtype and 16 B-aligned
 
 int64_t fp8_pack_bytes(const std::vector<at::Tensor>& tensors, int64_t world) {
   auto g = pack_geometry(tensors, world);
@@ -80,48 +170,34 @@ int64_t fp8_slice_bytes(const std::vector<at::Tensor>& tensors, int64_t world) {
 
 void fp8_quantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
                   int64_t world) {
-  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
+  const int code = first_dtype_code(tensors, "fp8_quantize");
   auto g = pack_geometry(tensors, world);
   TORCH_CHECK(pack.numel() >= g.slice_bytes * world, "pack buffer too small");
-  auto meta = build_meta(tensors);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  auto st = tensors[0].scalar_type();
-  for (auto& t : tensors) TORCH_CHECK(t.scalar_type() == st, "mixed dtypes");
-  const int64_t* ptrs = meta.ptrs.data_ptr<int64_t>();
-  const int64_t* prefix = meta.prefix.data_ptr<int64_t>();
-  const int64_t* numels = meta.numels.data_ptr<int64_t>();
-  uint8_t* p = pack.data_ptr<uint8_t>();
-  int code = st == at::kBFloat16 ? 0 : st == at::kHalf ? 1 : st == at::kFloat ? 2 : -1;
-  TORCH_CHECK(code >= 0, "unsupported dtype for fp8 quantize: ", st);
-  tft::launch_quantize_dtype(code, ptrs, prefix, numels, (int)tensors.size(),
-                             g.total_blocks, g.padded_blocks, g.blocks_per_rank,
-                             g.slice_bytes, p, (tft_stream)stream);
+  TableSet tables(tensors[0], "fp8_quantize", /*need_16b_alignment=*/true);
+  const int h = tables.add({{&tensors, tensors[0].scalar_type()}});
+  tables.upload();
+  tft::launch_quantize_dtype(code, tables.table(h), g.padded_blocks, g.blocks_per_rank,
+                             g.slice_bytes, pack.data_ptr<uint8_t>(), current_stream());
 }
 
 void fp8_dequantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
                     int64_t world) {
-  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
+  const int code = first_dtype_code(tensors, "fp8_dequantize");
   auto g = pack_geometry(tensors, world);
-  auto meta = build_meta(tensors);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  auto st = tensors[0].scalar_type();
-  const int64_t* ptrs = meta.ptrs.data_ptr<int64_t>();
-  const int64_t* prefix = meta.prefix.data_ptr<int64_t>();
-  const int64_t* numels = meta.numels.data_ptr<int64_t>();
-  const uint8_t* p = pack.data_ptr<uint8_t>();
-  int code = st == at::kBFloat16 ? 0 : st == at::kHalf ? 1 : st == at::kFloat ? 2 : -1;
-  TORCH_CHECK(code >= 0, "unsupported dtype for fp8 dequantize: ", st);
-  tft::launch_dequantize_dtype(code, ptrs, prefix, numels, (int)tensors.size(),
-                               g.total_blocks, g.padded_blocks, g.blocks_per_rank,
-                               g.slice_bytes, p, (tft_stream)stream);
+  TableSet tables(tensors[0], "fp8_dequantize", /*need_16b_alignment=*/true);
+  const int h = tables.add({{&tensors, tensors[0].scalar_type()}});
+  tables.upload();
+  tft::launch_dequantize_dtype(code, tables.table(h), g.padded_blocks,
+                               g.blocks_per_rank, g.slice_bytes,
+                               pack.data_ptr<uint8_t>(), current_stream());
 }
 
 void fp8_reduce(at::Tensor recv, at::Tensor out, int64_t world, bool avg) {
   TORCH_CHECK(recv.is_cuda() && out.is_cuda());
   TORCH_CHECK(recv.numel() == out.numel() * world, "recv must hold world slices");
   const int64_t slice_bytes = out.numel();
-  const int64_t blocks_per_rank = slice_bytes / (4 + kQBlock);
-  TORCH_CHECK(blocks_per_rank * (4 + kQBlock) == slice_bytes, "bad slice size");
+  const int64_t blocks_per_rank = slice_bytes / (4 + tft::kMtBlock);
+  TORCH_CHECK(blocks_per_rank * (4 + tft::kMtBlock) == slice_bytes, "bad slice size");
   auto stream = at::cuda::getCurrentCUDAStream().stream();
   tft::launch_reduce(recv.data_ptr<uint8_t>(), out.data_ptr<uint8_t>(), (int)world,
                      blocks_per_rank, slice_bytes, avg, (tft_stream)stream);
@@ -238,92 +314,38 @@ void adamw_step(const std::vector<at::Tensor>& params,
                 const std::vector<at::Tensor>& exp_avg_sqs, double lr,
                 double beta1, double beta2, double eps, double weight_decay,
                 int64_t step) {
-  const int64_t n = (int64_t)params.size();
-  TORCH_CHECK(n > 0);
-  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
-  at::Tensor host = at::empty({6 * n + 1}, opts);
-  int64_t* h = host.data_ptr<int64_t>();
-  int64_t acc = 0;
-  for (int64_t i = 0; i < n; i++) {
-    TORCH_CHECK(params[i].is_contiguous() && grads[i].is_contiguous());
-    TORCH_CHECK(params[i].scalar_type() == at::kBFloat16, "params must be bf16");
-    TORCH_CHECK(exp_avgs[i].scalar_type() == at::kFloat, "states must be fp32");
-    h[i] = (int64_t)params[i].data_ptr();
-    h[n + i] = (int64_t)grads[i].data_ptr();
-    h[2 * n + i] = (int64_t)exp_avgs[i].data_ptr();
-    h[3 * n + i] = (int64_t)exp_avg_sqs[i].data_ptr();
-    h[4 * n + i] = params[i].numel();
-    h[5 * n + i] = acc;
-    acc += (params[i].numel() + kQBlock - 1) / kQBlock;
-  }
-  h[6 * n] = acc;
-  at::Tensor dev = host.to(params[0].device(), /*non_blocking=*/true);
-  const int64_t* d = dev.data_ptr<int64_t>();
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
+  TORCH_CHECK(!params.empty(), "adamw_step: need at least one tensor");
+  TableSet tables(params[0], "adamw_step");
+  const int h = tables.add({{&params, at::kBFloat16},
+                            {&grads, at::kBFloat16},
+                            {&exp_avgs, at::kFloat},
+                            {&exp_avg_sqs, at::kFloat}});
+  tables.upload();
   const float bc1 = 1.0f - std::pow((float)beta1, (float)step);
   const float bc2 = 1.0f - std::pow((float)beta2, (float)step);
-  tft::launch_adamw(d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, (int)n,
-                    acc, (float)lr, (float)beta1, (float)beta2, (float)eps,
-                    (float)weight_decay, bc1, bc2, (tft_stream)stream);
+  tft::launch_adamw(tables.table(h), (float)lr, (float)beta1, (float)beta2, (float)eps,
+                    (float)weight_decay, bc1, bc2, current_stream());
 }
 
 // ---- global gradient norm / clip ---------------------------------------------
 
 namespace {
 
-// One device table per call: for every dtype present, [ptrs | numels |
-// block_prefix (n+1)] back to back, built in pinned memory and copied once.
-struct GradGroup {
-  int code = 0;  // dtype_code of kernels.h
-  std::vector<const at::Tensor*> ts;
-  int64_t off = 0;     // first int64 of this group's table
-  int64_t blocks = 0;  // logical 2048-element blocks
-};
-
+// One table per dtype present, all in one TableSet
 struct GradTables {
-  at::Tensor dev;
-  std::vector<GradGroup> groups;
+  TensorList by_dtype[3];  // indexed by dtype_code
+  int handle[3] = {-1, -1, -1};
 };
 
-GradTables build_grad_tables(const std::vector<at::Tensor>& tensors) {
-  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
-  GradTables tb;
-  tb.groups.resize(3);
-  for (int c = 0; c < 3; c++) tb.groups[c].code = c;
+void add_grad_tables(TableSet& tables, const TensorList& tensors, GradTables& gt) {
   for (auto& t : tensors) {
-    TORCH_CHECK(t.is_cuda(), "grad norm requires device tensors");
-    TORCH_CHECK(t.device() == tensors[0].device(), "tensors on different devices");
-    TORCH_CHECK(t.is_contiguous(), "grad norm requires contiguous tensors");
-    auto st = t.scalar_type();
-    int code = st == at::kBFloat16 ? 0 : st == at::kHalf ? 1 : st == at::kFloat ? 2 : -1;
-    TORCH_CHECK(code >= 0, "unsupported dtype for grad norm: ", st);
-    if (t.numel() > 0) tb.groups[code].ts.push_back(&t);
+    const int code = dtype_code(t.scalar_type());
+    TORCH_CHECK(code >= 0, "unsupported dtype for grad norm: ", t.scalar_type());
+    gt.by_dtype[code].push_back(t);
   }
-  int64_t words = 0;
-  for (auto& g : tb.groups) {
-    g.off = words;
-    if (!g.ts.empty()) words += 3 * (int64_t)g.ts.size() + 1;
-  }
-  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
-  at::Tensor host = at::empty({std::max<int64_t>(words, 1)}, opts);
-  int64_t* h = host.data_ptr<int64_t>();
-  for (auto& g : tb.groups) {
-    const int64_t n = (int64_t)g.ts.size();
-    int64_t* ptrs = h + g.off;
-    int64_t* numels = ptrs + n;
-    int64_t* prefix = numels + n;
-    int64_t acc = 0;
-    for (int64_t i = 0; i < n; i++) {
-      ptrs[i] = (int64_t)g.ts[i]->data_ptr();
-      numels[i] = g.ts[i]->numel();
-      prefix[i] = acc;
-      acc += (g.ts[i]->numel() + kQBlock - 1) / kQBlock;
-    }
-    if (n > 0) prefix[n] = acc;
-    g.blocks = acc;
-  }
-  tb.dev = host.to(tensors[0].device(), /*non_blocking=*/true);
-  return tb;
+  const at::ScalarType dtypes[3] = {at::kBFloat16, at::kHalf, at::kFloat};
+  for (int c = 0; c < 3; c++)
+    if (!gt.by_dtype[c].empty()) gt.handle[c] = tables.add({{&gt.by_dtype[c], dtypes[c]}});
 }
 
 void check_max_blocks(int64_t max_blocks) {
@@ -331,21 +353,17 @@ void check_max_blocks(int64_t max_blocks) {
               "max_blocks must be in [1, 65536], got ", max_blocks);
 }
 
-// partial sums per dtype group into one partials buffer, then one finalize
-void run_sumsq(const GradTables& tb, int64_t max_blocks, at::Tensor& stats,
-               tft_stream stream) {
+// partial sums of every table (dtype code, view) into one partials buffer,
+// then one finalize
+void run_sumsq(const std::vector<std::pair<int, tft::MultiTensorTable>>& tbs,
+               int64_t max_blocks, at::Tensor& stats, tft_stream stream) {
   int64_t n_partials = 0;
-  for (auto& g : tb.groups) n_partials += std::min(g.blocks, max_blocks);
+  for (auto& ct : tbs) n_partials += std::min(ct.second.total_blocks, max_blocks);
   auto partials = at::empty({n_partials}, stats.options());
-  const int64_t* d = tb.dev.data_ptr<int64_t>();
   int64_t at_partial = 0;
-  for (auto& g : tb.groups) {
-    const int64_t n = (int64_t)g.ts.size();
-    const int64_t grid = std::min(g.blocks, max_blocks);
-    if (grid == 0) continue;
-    const int64_t* base = d + g.off;
-    tft::launch_grad_sumsq_partial(g.code, base, base + n, base + 2 * n, (int)n,
-                                   g.blocks, (int)grid,
+  for (auto& ct : tbs) {
+    const int64_t grid = std::min(ct.second.total_blocks, max_blocks);
+    tft::launch_grad_sumsq_partial(ct.first, ct.second, (int)grid,
                                    partials.data_ptr<float>() + at_partial, stream);
     at_partial += grid;
   }
@@ -353,15 +371,26 @@ void run_sumsq(const GradTables& tb, int64_t max_blocks, at::Tensor& stats,
                                   stats.data_ptr<float>(), stream);
 }
 
+std::vector<std::pair<int, tft::MultiTensorTable>> grad_views(const TableSet& tables,
+                                                              const GradTables& gt) {
+  std::vector<std::pair<int, tft::MultiTensorTable>> out;
+  for (int c = 0; c < 3; c++)
+    if (gt.handle[c] >= 0) out.emplace_back(c, tables.table(gt.handle[c]));
+  return out;
+}
+
 }  // namespace
 
 // Sum of squares over every tensor, as a 1-element fp32 device tensor.
 at::Tensor grad_sumsq(const std::vector<at::Tensor>& tensors, int64_t max_blocks) {
   check_max_blocks(max_blocks);
-  auto tb = build_grad_tables(tensors);
+  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
+  TableSet tables(tensors[0], "grad norm");
+  GradTables gt;
+  add_grad_tables(tables, tensors, gt);
+  tables.upload();
   auto stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  run_sumsq(tb, max_blocks, stats, (tft_stream)stream);
+  run_sumsq(grad_views(tables, gt), max_blocks, stats, current_stream());
   return stats;
 }
 
@@ -371,20 +400,19 @@ at::Tensor clip_grad_norm(const std::vector<at::Tensor>& tensors, double max_nor
                           int64_t max_blocks, py::object norm_reduce) {
   check_max_blocks(max_blocks);
   TORCH_CHECK(max_norm > 0.0, "max_norm must be > 0");
-  auto tb = build_grad_tables(tensors);
+  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
+  TableSet tables(tensors[0], "grad norm");
+  GradTables gt;
+  add_grad_tables(tables, tensors, gt);
+  tables.upload();
   auto stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  run_sumsq(tb, max_blocks, stats, (tft_stream)stream);
+  auto stream = current_stream();
+  const auto views = grad_views(tables, gt);
+  run_sumsq(views, max_blocks, stats, stream);
   if (!norm_reduce.is_none()) norm_reduce(stats);
-  const int64_t* d = tb.dev.data_ptr<int64_t>();
-  for (auto& g : tb.groups) {
-    const int64_t n = (int64_t)g.ts.size();
-    if (n == 0) continue;
-    const int64_t* base = d + g.off;
-    tft::launch_grad_scale(g.code, base, base + n, base + 2 * n, (int)n, g.blocks,
-                           stats.data_ptr<float>(), (float)max_norm,
-                           (tft_stream)stream);
-  }
+  for (auto& ct : views)
+    tft::launch_grad_scale(ct.first, ct.second, stats.data_ptr<float>(), (float)max_norm,
+                           stream);
   return stats;
 }
 
@@ -407,9 +435,7 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
                      at::Tensor norm_out, py::object norm_reduce) {
   const int64_t n = (int64_t)params.size();
   const int64_t ng = (int64_t)group_sizes.size();
-  TORCH_CHECK(n > 0);
-  TORCH_CHECK((int64_t)grads.size() == n && (int64_t)exp_avgs.size() == n &&
-              (int64_t)exp_avg_sqs.size() == n && (int64_t)steps.size() == n);
+  TORCH_CHECK(n > 0, "adamw_clip_step: need at least one tensor");
   TORCH_CHECK((int64_t)lrs.size() == ng && (int64_t)beta1s.size() == ng &&
               (int64_t)beta2s.size() == ng && (int64_t)epss.size() == ng &&
               (int64_t)weight_decays.size() == ng);
@@ -423,159 +449,53 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
   TORCH_CHECK(skipped.device() == dev && skipped.scalar_type() == at::kInt &&
               skipped.numel() == 1);
 
-  // [param | grad | m | v | numel | step | prefix over all (n+1) |
-  //  per-group prefixes (size_g + 1 each)]
-  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
-  at::Tensor host = at::empty({8 * n + 1 + ng}, opts);
-  int64_t* h = host.data_ptr<int64_t>();
-  int64_t* gprefix = h + 6 * n;
-  int64_t* uprefix = h + 7 * n + 1;
-  int64_t acc = 0;
-  for (int64_t i = 0; i < n; i++) {
-    TORCH_CHECK(params[i].is_cuda() && params[i].device() == dev &&
-                grads[i].device() == dev && exp_avgs[i].device() == dev &&
-                exp_avg_sqs[i].device() == dev && steps[i].device() == dev,
-                "all tensors must be on the same device");
-    TORCH_CHECK(params[i].is_contiguous() && grads[i].is_contiguous() &&
-                exp_avgs[i].is_contiguous() && exp_avg_sqs[i].is_contiguous());
-    TORCH_CHECK(params[i].scalar_type() == at::kBFloat16 &&
-                grads[i].scalar_type() == at::kBFloat16,
-                "params and grads must be bf16");
-    TORCH_CHECK(exp_avgs[i].scalar_type() == at::kFloat &&
-                exp_avg_sqs[i].scalar_type() == at::kFloat, "states must be fp32");
-    const int64_t ne = params[i].numel();
-    TORCH_CHECK(grads[i].numel() == ne && exp_avgs[i].numel() == ne &&
-                exp_avg_sqs[i].numel() == ne, "size mismatch");
-    TORCH_CHECK(steps[i].scalar_type() == at::kInt && steps[i].numel() == 1,
-                "step must be a 1-element int32 device tensor");
-    h[i] = (int64_t)params[i].data_ptr();
-    h[n + i] = (int64_t)grads[i].data_ptr();
-    h[2 * n + i] = (int64_t)exp_avgs[i].data_ptr();
-    h[3 * n + i] = (int64_t)exp_avg_sqs[i].data_ptr();
-    h[4 * n + i] = ne;
-    h[5 * n + i] = (int64_t)steps[i].data_ptr();
-    gprefix[i] = acc;
-    acc += (ne + kQBlock - 1) / kQBlock;
+  // one norm table over every gradient, one update table per param group
+  // (its prefix starts at 0 again), and every step count for the bump launch,
+  // those of zero-numel parameters included
+  TableSet tables(params[0], "adamw_clip_step");
+  const int h_norm = tables.add({{&grads, at::kBFloat16}});
+  std::vector<int> h_update(ng);
+  int64_t first = 0;
+  for (int64_t g = 0; g < ng; g++) {
+    TORCH_CHECK(group_sizes[g] >= 0 && first + group_sizes[g] <= n);
+    h_update[g] = tables.add({{&params, at::kBFloat16},
+                              {&grads, at::kBFloat16},
+                              {&exp_avgs, at::kFloat},
+                              {&exp_avg_sqs, at::kFloat},
+                              {&steps, at::kInt, /*one_element=*/true}},
+                             first, group_sizes[g]);
+    first += group_sizes[g];
   }
-  gprefix[n] = acc;
-  std::vector<int64_t> group_blocks(ng, 0);
-  {
-    int64_t first = 0, w = 0;
-    for (int64_t g = 0; g < ng; g++) {
-      TORCH_CHECK(group_sizes[g] >= 0 && first + group_sizes[g] <= n);
-      for (int64_t i = 0; i <= group_sizes[g]; i++)
-        uprefix[w + i] = gprefix[first + i] - gprefix[first];
-      group_blocks[g] = gprefix[first + group_sizes[g]] - gprefix[first];
-      w += group_sizes[g] + 1;
-      first += group_sizes[g];
-    }
-    TORCH_CHECK(first == n, "group_sizes must cover every tensor");
-  }
-  at::Tensor table = host.to(dev, /*non_blocking=*/true);
-  const int64_t* d = table.data_ptr<int64_t>();
-  auto stream = (tft_stream)at::cuda::getCurrentCUDAStream().stream();
+  TORCH_CHECK(first == n, "group_sizes must cover every tensor");
+  const int h_steps = tables.add({{&steps, at::kInt, /*one_element=*/true}});
+  tables.upload();
+  auto stream = current_stream();
 
-  const int64_t grid = std::min(acc, max_blocks);
-  auto partials = at::empty({grid}, stats.options());
-  tft::launch_grad_sumsq_partial(0, d + n, d + 4 * n, d + 6 * n, (int)n, acc,
-                                 (int)grid, partials.data_ptr<float>(), stream);
-  tft::launch_grad_sumsq_finalize(partials.data_ptr<float>(), (int)grid,
-                                  stats.data_ptr<float>(), stream);
+  run_sumsq({{tft::kBF16, tables.table(h_norm)}}, max_blocks, stats, stream);
   if (!norm_reduce.is_none()) norm_reduce(stats.narrow(0, 0, 1));
 
-  int64_t first = 0, w = 0;
-  for (int64_t g = 0; g < ng; g++) {
-    const int64_t cnt = group_sizes[g];
-    if (cnt > 0)
-      tft::launch_adamw_clip(d + first, d + n + first, d + 2 * n + first,
-                             d + 3 * n + first, d + 4 * n + first,
-                             d + 7 * n + 1 + w, d + 5 * n + first, (int)cnt,
-                             group_blocks[g], (float)lrs[g], (float)beta1s[g],
-                             (float)beta2s[g], (float)epss[g],
-                             (float)weight_decays[g], stats.data_ptr<float>(),
-                             (float)max_norm, stream);
-    w += cnt + 1;
-    first += cnt;
-  }
-  tft::launch_adamw_bump_steps(d + 5 * n, (int)n, stats.data_ptr<float>(),
+  for (int64_t g = 0; g < ng; g++)
+    tft::launch_adamw_clip(tables.table(h_update[g]), (float)lrs[g], (float)beta1s[g],
+                           (float)beta2s[g], (float)epss[g], (float)weight_decays[g],
+                           stats.data_ptr<float>(), (float)max_norm, stream);
+  const auto st = tables.table(h_steps);
+  tft::launch_adamw_bump_steps(st.col(0), st.n, stats.data_ptr<float>(),
                                skipped.data_ptr<int>(), norm_out.data_ptr<float>(),
                                stream);
 }
 
 // ---- fused DiLoCo outer sync ---------------------------------------------------
 
-namespace {
-
-// One pinned table for `lists.size()` parallel tensor lists of one dtype:
-// [ptrs of list 0 | ... | ptrs of list k-1 | numels | block_prefix (n+1)],
-// with zero-numel tensors left out. Copied to the device once.
-struct SyncTable {
-  at::Tensor dev;
-  int64_t n = 0;       // tensors kept
-  int64_t blocks = 0;  // logical 2048-element blocks
-  int code = 0;        // dtype_code of kernels.h
-};
-
-SyncTable build_sync_table(const std::vector<const std::vector<at::Tensor>*>& lists,
-                           const char* what) {
-  const int64_t k = (int64_t)lists.size();
-  const auto& first = *lists[0];
-  const int64_t n_all = (int64_t)first.size();
-  TORCH_CHECK(n_all > 0, what, ": need at least one tensor");
-  const auto dev = first[0].device();
-  const auto st = first[0].scalar_type();
-  SyncTable tb;
-  tb.code = st == at::kBFloat16 ? 0 : st == at::kHalf ? 1 : st == at::kFloat ? 2 : -1;
-  TORCH_CHECK(tb.code >= 0, what, ": unsupported dtype ", st);
-  std::vector<int64_t> keep;
-  for (int64_t i = 0; i < n_all; i++) {
-    for (int64_t j = 0; j < k; j++) {
-      TORCH_CHECK((int64_t)lists[j]->size() == n_all, what, ": list lengths differ");
-      const auto& t = (*lists[j])[i];
-      TORCH_CHECK(t.is_cuda() && t.device() == dev, what,
-                  ": all tensors must be on one device");
-      TORCH_CHECK(t.scalar_type() == st, what, ": mixed dtypes (", st, " and ",
-                  t.scalar_type(), ")");
-      TORCH_CHECK(t.is_contiguous(), what, ": tensors must be contiguous");
-      TORCH_CHECK(t.numel() == first[i].numel(), what, ": size mismatch at tensor ", i);
-    }
-    if (first[i].numel() > 0) keep.push_back(i);
-  }
-  tb.n = (int64_t)keep.size();
-  if (tb.n == 0) return tb;
-  const int64_t n = tb.n;
-  auto opts = at::TensorOptions().dtype(at::kLong).pinned_memory(true);
-  at::Tensor host = at::empty({(k + 2) * n + 1}, opts);
-  int64_t* h = host.data_ptr<int64_t>();
-  int64_t* numels = h + k * n;
-  int64_t* prefix = h + (k + 1) * n;
-  int64_t acc = 0;
-  for (int64_t i = 0; i < n; i++) {
-    for (int64_t j = 0; j < k; j++) h[j * n + i] = (int64_t)(*lists[j])[keep[i]].data_ptr();
-    numels[i] = first[keep[i]].numel();
-    prefix[i] = acc;
-    acc += (numels[i] + kQBlock - 1) / kQBlock;
-  }
-  prefix[n] = acc;
-  TORCH_CHECK(acc < (int64_t(1) << 31), what, ": too many elements for one launch");
-  tb.blocks = acc;
-  tb.dev = host.to(dev, /*non_blocking=*/true);
-  return tb;
-}
-
-}  // namespace
-
 // outs[i] = minuends[i] - subtrahends[i], one launch for the whole list
 void diloco_pseudograd(const std::vector<at::Tensor>& outs,
                        const std::vector<at::Tensor>& minuends,
                        const std::vector<at::Tensor>& subtrahends) {
-  auto tb = build_sync_table({&outs, &minuends, &subtrahends}, "pseudograd_");
-  if (tb.n == 0) return;
-  const int64_t n = tb.n;
-  const int64_t* d = tb.dev.data_ptr<int64_t>();
-  auto stream = (tft_stream)at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_pseudograd(tb.code, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, (int)n,
-                         tb.blocks, stream);
+  const int code = first_dtype_code(outs, "pseudograd_");
+  const auto st = outs[0].scalar_type();
+  TableSet tables(outs[0], "pseudograd_");
+  const int h = tables.add({{&outs, st}, {&minuends, st}, {&subtrahends, st}});
+  tables.upload();
+  tft::launch_pseudograd(code, tables.table(h), current_stream());
 }
 
 // Outer SGD step + re-snapshot + lerp for one param group; momentum_bufs is
@@ -590,18 +510,15 @@ void diloco_outer_step(const std::vector<at::Tensor>& snapshots,
               "diloco_outer_step_: momentum buffers are needed exactly when "
               "momentum != 0");
   TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "alpha must be in [0, 1], got ", alpha);
-  std::vector<const std::vector<at::Tensor>*> lists = {&snapshots, &params, &pseudograds};
-  if (has_m) lists.push_back(&momentum_bufs);
-  auto tb = build_sync_table(lists, "diloco_outer_step_");
-  if (tb.n == 0) return;
-  const int64_t n = tb.n;
-  const int64_t k = (int64_t)lists.size();
-  const int64_t* d = tb.dev.data_ptr<int64_t>();
-  auto stream = (tft_stream)at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_outer_sgd(tb.code, has_m, d, d + n, d + 2 * n,
-                        has_m ? d + 3 * n : nullptr, d + k * n, d + (k + 1) * n, (int)n,
-                        tb.blocks, (float)lr, (float)momentum, nesterov, (float)alpha,
-                        stream);
+  const int code = first_dtype_code(snapshots, "diloco_outer_step_");
+  const auto st = snapshots[0].scalar_type();
+  std::vector<Column> cols = {{&snapshots, st}, {&params, st}, {&pseudograds, st}};
+  if (has_m) cols.push_back({&momentum_bufs, st});
+  TableSet tables(snapshots[0], "diloco_outer_step_");
+  const int h = tables.add(cols);
+  tables.upload();
+  tft::launch_outer_sgd(code, has_m, tables.table(h), (float)lr, (float)momentum,
+                        nesterov, (float)alpha, current_stream());
 }
 
 // ---- flash attention backward (appended) -----------------------------------

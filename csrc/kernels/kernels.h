@@ -8,23 +8,51 @@
 struct ihipStream_t;
 using tft_stream = ihipStream_t*;
 
+// callable from kernels when a HIP compiler reads this header
+#if defined(__HIP__)
+#define TFT_HD __host__ __device__
+#else
+#define TFT_HD
+#endif
+
 namespace torchft_amd {
 
+// Multi-tensor addressing (docs/KERNELS.md, "Shared conventions") -----------
+// Tensors are cut into logical blocks of kMtBlock elements; a workgroup of
+// kMtThreads lanes handles one block, kMtEpt elements per lane.
+constexpr int kMtBlock = 2048;
+constexpr int kMtThreads = 256;
+constexpr int kMtEpt = 8;
+static_assert(kMtBlock == kMtThreads * kMtEpt, "one lane per kMtEpt elements");
+
+enum DtypeCode : int { kBF16 = 0, kF16 = 1, kF32 = 2 };
+
+// View of one device table of n tensors (rows) and n_cols pointer columns:
+//   [col 0 | ... | col n_cols-1 | numels | block_prefix (n+1)]
+// every column n int64 entries; tensor t owns the logical blocks
+// [prefix()[t], prefix()[t+1]). Passed to launchers and kernels by value.
+struct MultiTensorTable {
+  const int64_t* base;
+  int n;
+  int n_cols;
+  int64_t total_blocks;
+
+  TFT_HD const int64_t* col(int j) const { return base + (int64_t)j * n; }
+  TFT_HD const int64_t* numels() const { return col(n_cols); }
+  TFT_HD const int64_t* prefix() const { return col(n_cols + 1); }
+};
+
 // fp8_quant.hip ------------------------------------------------------------
-// dtype_code: 0 = bf16, 1 = fp16, 2 = fp32
-void launch_quantize_dtype(int dtype_code, const int64_t* ptrs,
-                           const int64_t* block_prefix, const int64_t* numels,
-                           int n_tensors, int64_t total_blocks,
+// table: col 0 = the tensors, every one 16 B-aligned (the bindings check).
+// The grid is padded_blocks workgroups; blocks at or past tb.total_blocks are
+// padding slots of the pack.
+void launch_quantize_dtype(int dtype_code, MultiTensorTable tb,
                            int64_t padded_blocks, int64_t blocks_per_rank,
                            int64_t slice_bytes, uint8_t* pack, tft_stream stream);
-
-void launch_dequantize_dtype(int dtype_code, const int64_t* ptrs,
-                             const int64_t* block_prefix, const int64_t* numels,
-                             int n_tensors, int64_t total_blocks,
+void launch_dequantize_dtype(int dtype_code, MultiTensorTable tb,
                              int64_t padded_blocks, int64_t blocks_per_rank,
                              int64_t slice_bytes, const uint8_t* pack,
                              tft_stream stream);
-
 void launch_reduce(const uint8_t* in, uint8_t* out, int world,
                    int64_t blocks_per_rank, int64_t slice_bytes, bool avg,
                    tft_stream stream);
@@ -48,21 +76,14 @@ void launch_swiglu_bwd(const void* dy, const void* a, const void* b, void* da,
                        void* db, int64_t n, tft_stream stream);
 
 // fused_adamw.hip ----------------------------------------------------------
-void launch_adamw(const int64_t* param_ptrs, const int64_t* grad_ptrs,
-                  const int64_t* m_ptrs, const int64_t* v_ptrs,
-                  const int64_t* numels, const int64_t* block_prefix,
-                  int n_tensors, int64_t total_blocks, float lr, float beta1,
-                  float beta2, float eps, float weight_decay,
-                  float bias_correction1, float bias_correction2,
-                  tft_stream stream);
-// clip mode: coefficient from stats[0] (global sum of squared gradients),
-// bias corrections from the per-tensor device int32 step counts; a
-// non-finite norm stores nothing
-void launch_adamw_clip(const int64_t* param_ptrs, const int64_t* grad_ptrs,
-                       const int64_t* m_ptrs, const int64_t* v_ptrs,
-                       const int64_t* numels, const int64_t* block_prefix,
-                       const int64_t* step_ptrs, int n_tensors,
-                       int64_t total_blocks, float lr, float beta1, float beta2,
+// table: cols 0..3 = param, grad, exp_avg, exp_avg_sq (bf16, bf16, fp32, fp32)
+void launch_adamw(MultiTensorTable tb, float lr, float beta1, float beta2,
+                  float eps, float weight_decay, float bias_correction1,
+                  float bias_correction2, tft_stream stream);
+// clip mode: col 4 = the per-tensor device int32 step counts the bias
+// corrections come from; coefficient from stats[0] (global sum of squared
+// gradients); a non-finite norm stores nothing
+void launch_adamw_clip(MultiTensorTable tb, float lr, float beta1, float beta2,
                        float eps, float weight_decay, const float* stats,
                        float max_norm, tft_stream stream);
 // finite norm: ++*step[t] for every tensor; else ++*skipped. norm_out[0] = norm
@@ -71,24 +92,27 @@ void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,
                              tft_stream stream);
 
 // grad_norm.hip ------------------------------------------------------------
-// dtype_code as above. `grid` workgroups grid-stride over total_blocks logical
-// blocks and write partials[0..grid); finalize sums n_partials of them in
-// double into stats[0] (the sum of squares, fp32).
-void launch_grad_sumsq_partial(int dtype_code, const int64_t* ptrs,
-                               const int64_t* numels, const int64_t* block_prefix,
-                               int n_tensors, int64_t total_blocks, int grid,
+// table: col 0 = the gradients. `grid` workgroups grid-stride over the
+// logical blocks and write partials[0..grid); finalize sums n_partials of
+// them in double into stats[0] (the sum of squares, fp32).
+void launch_grad_sumsq_partial(int dtype_code, MultiTensorTable tb, int grid,
                                float* partials, tft_stream stream);
 void launch_grad_sumsq_finalize(const float* partials, int n_partials, float* stats,
                                 tft_stream stream);
 // in place g *= min(1, max_norm / (sqrt(stats[0]) + 1e-6)); no-op if non-finite
-void launch_grad_scale(int dtype_code, const int64_t* ptrs, const int64_t* numels,
-                       const int64_t* block_prefix, int n_tensors,
-                       int64_t total_blocks, const float* stats, float max_norm,
-                       tft_stream stream);
+void launch_grad_scale(int dtype_code, MultiTensorTable tb, const float* stats,
+                       float max_norm, tft_stream stream);
 
-}  // namespace torchft_amd
-
-namespace torchft_amd {
+// diloco_sync.hip -----------------------------------------------------------
+// every tensor of one call has the dtype of dtype_code.
+// cols 0..2 = out, a, b: out[t] = a[t] - b[t], one rounding
+void launch_pseudograd(int dtype_code, MultiTensorTable tb, tft_stream stream);
+// cols 0..2 = g, l, d (col 3 = m when has_momentum): outer SGD on the
+// snapshots g from the pseudo-gradients d, then l <- lerp(new g, l, alpha);
+// g, m, l in place
+void launch_outer_sgd(int dtype_code, bool has_momentum, MultiTensorTable tb,
+                      float lr, float mu, bool nesterov, float alpha,
+                      tft_stream stream);
 
 // flash_attn_bwd.hip --------------------------------------------------------
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
@@ -108,22 +132,6 @@ void launch_cross_entropy(void* logits, const int64_t* targets, float* row_loss,
                           const float* grad_scale, int64_t rows, int V,
                           int64_t ignore_index, float z_loss, bool write_grad,
                           tft_stream stream);
-
-// diloco_sync.hip -----------------------------------------------------------
-// dtype_code as above; every tensor of one call has that dtype.
-// out[t] = a[t] - b[t], one rounding
-void launch_pseudograd(int dtype_code, const int64_t* out_ptrs, const int64_t* a_ptrs,
-                       const int64_t* b_ptrs, const int64_t* numels,
-                       const int64_t* block_prefix, int n_tensors,
-                       int64_t total_blocks, tft_stream stream);
-// outer SGD on the snapshots g from the pseudo-gradients d (momentum buffers m
-// read only when has_momentum), then l <- lerp(new g, l, alpha); g, m, l in place
-void launch_outer_sgd(int dtype_code, bool has_momentum, const int64_t* g_ptrs,
-                      const int64_t* l_ptrs, const int64_t* d_ptrs,
-                      const int64_t* m_ptrs, const int64_t* numels,
-                      const int64_t* block_prefix, int n_tensors,
-                      int64_t total_blocks, float lr, float mu, bool nesterov,
-                      float alpha, tft_stream stream);
 
 // mfma_probe.hip ------------------------------------------------------------
 void launch_mfma_probe(const void* A, const void* B, float* D, tft_stream s);

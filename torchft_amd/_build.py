@@ -69,7 +69,7 @@ def build_hip_kernels(force: bool = False) -> Path | None:
     """
     src_dir = CSRC / "kernels"
     sources = sorted(src_dir.glob("*.hip")) + [src_dir / "bindings.cpp"]
-    headers = [src_dir / "kernels.h"]
+    headers = sorted(src_dir.glob("*.h"))
     out = PKG / "_hip_kernels.so"
     if not force and _newer(out, sources + headers):
         return out
