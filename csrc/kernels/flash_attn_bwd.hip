@@ -9,7 +9,7 @@
 //
 // Structure (FA2 split): kernel 1 computes dK/dV (grid over KV blocks),
 // kernel 2 computes dQ (grid over Q blocks); both recompute S/P per tile.
-// Each workgroup = 4 wave64s; each wave owns one 32-row block and holds its
+// Each workgroup = 8 wave64s; each wave owns one 32-row block and holds its
 // fp32 accumulators in the unified VGPR/AGPR file.
 //
 // Schedule (v3): the staged tiles live in ONE subtiled row-major LDS image
@@ -24,6 +24,15 @@
 // The 1040-B subtile stride (65 x 16 B) makes the 8 staging ds_write_b128
 // of a wave's lane group land on 8 distinct bank quads (1024 would be
 // 8-way conflicted).
+//
+// Pipeline (v4): both tile streams are software-pipelined one tile deep
+// (T14 async-STAGE split). A prologue stages tile 0; each iteration issues
+// tile t+1's global loads into registers, computes tile t from img[t&1],
+// then writes the registers to img[(t+1)&1] and takes ONE barrier. Only one
+// workgroup fits a CU, so nothing else would cover the L2/HBM round trip.
+// dkdv issues the prefetch between its two phases, which also lets the
+// dV/dK phase double-buffer its tr_b16 reads. The arithmetic is untouched:
+// results are bit-identical to the v3 loop.
 //
 // MFMA lane mappings (verified by mfma_probe.hip on gfx950):
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
@@ -119,6 +128,12 @@ __device__ inline bf16x8_vec pb_afrag(const unsigned char* pb, int h2, int half,
 }
 __device__ inline int c_row(int reg, int half) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * half;
+}
+// pa/pb address of a lane's C element (row c_row(4*r4, half), col l31).
+// The four rows c_row(4*r4 + r, half), r = 0..3, share one swizzle key, so
+// they sit at +64*r: 4 address registers serve the 16 stores, not 16.
+__device__ inline int pb_row4_addr(int r4, int half, int l31) {
+  return pb_addr(8 * r4 + 4 * half, l31 * 2);
 }
 
 // per-lane invariant part of every tr_b16 address (see header):
@@ -220,21 +235,25 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
 
   const unsigned tr_off = tr_lane_off(lane);
 
+  // prologue: stage tile 0 and its row statistics
+  TileRegs nxt = load_tiles(tile_src(0, q), tile_src(0, dout), q_ld);
+  float lse_n = lse_base[i_min * FA_BLK + l31];
+  float delta_n = delta_base[i_min * FA_BLK + l31];
+  write_tiles(&sm.img[0], nxt);
+  __syncthreads();
+
   for (int t = 0; t < T; t++) {
     const int cur = t & 1;
-    const int g = t / nI;
     const int i = i_min + t % nI;
 
-    {
-      TileRegs r = load_tiles(tile_src(t, q), tile_src(t, dout), q_ld);
-      write_tiles(&sm.img[cur], r);
-    }
-    __syncthreads();
+    const float lse_q = lse_n;
+    const float delta_q = delta_n;
+    const bool more = t + 1 < T;  // wave-uniform
+    const bool computes = active && !(causal && i < jb);
 
-    if (active && !(causal && i < jb)) {
+    // phase 1: S^T, dP^T, then P / dS into the wave's pa / pb
+    if (computes) {
       const ImageSet* img = &sm.img[cur];
-      const float lse_q = lse_base[(int64_t)g * S + i * FA_BLK + l31];
-      const float delta_q = delta_base[(int64_t)g * S + i * FA_BLK + l31];
 
       // interleaved S^T / dP^T chains (independent accumulators)
       f32x16 s_acc = {};
@@ -253,31 +272,61 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
             vf, rm_bfrag(img->b.sub, tt, half, l31), dp_acc, 0, 0, 0);
       }
 
-      const int qg = i * FA_BLK + l31;
       unsigned char* pa = sm.pa[wave];
       unsigned char* pb = sm.pb[wave];
+      // q row minus the lane's first key row: the causal test of C register
+      // rg is one compare against the constant c_row(rg, 0)
+      const int qk = (i - jb) * FA_BLK + l31 - 4 * half;
 #pragma unroll
       for (int rg = 0; rg < 16; rg++) {
-        const int row = c_row(rg, half);
-        const int kg = jb * FA_BLK + row;
-        const bool valid = !causal || (qg >= kg);
+        const bool valid = !causal || (qk >= c_row(rg, 0));
         const float pv = valid ? __expf(scale * s_acc[rg] - lse_q) : 0.0f;
-        *reinterpret_cast<bf16*>(pa + pb_addr(row, l31 * 2)) = __float2bfloat16(pv);
-        *reinterpret_cast<bf16*>(pb + pb_addr(row, l31 * 2)) =
+        const int wr = pb_row4_addr(rg >> 2, half, l31) + (rg & 3) * 64;
+        *reinterpret_cast<bf16*>(pa + wr) = __float2bfloat16(pv);
+        *reinterpret_cast<bf16*>(pb + wr) =
             __float2bfloat16(pv * (dp_acc[rg] - delta_q) * scale);
       }
-      // dV += P^T dO ; dK += dS^T Q — B-fragments by hardware transpose,
+    }
+
+    // T14 split: tile t+1's global loads (and its lse/delta rows) issue
+    // here, once the S/dP accumulators are dead (no VGPR cost at the
+    // pressure peak), and land under the dV/dK MFMAs; the LDS write follows
+    // the compute. Every wave takes part, computing or not. The last tile
+    // forms no address.
+    if (more) {
+      const int64_t st = (int64_t)((t + 1) / nI) * S +
+                         (i_min + (t + 1) % nI) * FA_BLK + l31;
+      nxt = load_tiles(tile_src(t + 1, q), tile_src(t + 1, dout), q_ld);
+      lse_n = lse_base[st];
+      delta_n = delta_base[st];
+    }
+
+    if (computes) {
+      const ImageSet* img = &sm.img[cur];
+      unsigned char* pa = sm.pa[wave];
+      unsigned char* pb = sm.pb[wave];
+      // phase 2: dV += P^T dO ; dK += dS^T Q. A-fragments (P, dS) come
+      // from the wave-private pa / pb (same-wave DS ordering covers the RAW
+      // with the stores of phase 1); B-fragments by hardware transpose,
       // software-pipelined one (dt,h2) iteration ahead: the next
       // iteration's 4 tr reads issue before this one's MFMAs, and the
       // counted lgkmcnt(4) leaves exactly those in flight (safe beside
       // compiler DS ops: DS completes in order, so "all but newest 4 done"
-      // over-waits at worst).
+      // over-waits at worst). The second register set fits because phase 2
+      // no longer shares its pressure peak with the S/dP accumulators.
       const unsigned a_base = (unsigned)(uintptr_t)img->a.sub + tr_off;
       const unsigned b_base = (unsigned)(uintptr_t)img->b.sub + tr_off;
-      // single-buffered tr reads: at 2 waves/SIMD the partner wave's MFMAs
-      // cover the read latency, and the freed registers keep the kernel
-      // off the 256-VGPR spill cliff (a spilled kfrag put a scratch reload
-      // + vmcnt(0) drain inside this loop)
+      bf16x8_vec paf[2], pbf[2];
+#pragma unroll
+      for (int h2 = 0; h2 < 2; h2++) {
+        paf[h2] = pb_afrag(pa, h2, half, l31);
+        pbf[h2] = pb_afrag(pb, h2, half, l31);
+      }
+      unsigned long long fd0[2], fd1[2], fq0[2], fq1[2];
+      TR_READ(fd0[0], b_base);
+      TR_READ(fd1[0], b_base + 128);
+      TR_READ(fq0[0], a_base);
+      TR_READ(fq1[0], a_base + 128);
 #pragma unroll
       for (int it = 0; it < 8; it++) {
         // dt fastest: consecutive MFMAs rotate over the four dv/dk
@@ -285,23 +334,28 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
         // the 32x32 MFMA never stalls the pipe (PMC: SQ_WAIT_INST_ANY)
         const int dt = it & 3;
         const int h2 = it >> 2;
-        const unsigned base = dt * (2 * SUBT) + h2 * 512;
-        unsigned long long fd0, fd1, fq0, fq1;
-        TR_READ(fd0, b_base + base);        // dO rows +0..3
-        TR_READ(fd1, b_base + base + 128);  // dO rows +4..7
-        TR_READ(fq0, a_base + base);        // Q  rows +0..3
-        TR_READ(fq1, a_base + base + 128);  // Q  rows +4..7
-        TR_WAIT4_KEEP(0, fd0, fd1, fq0, fq1);
-        // pa/pb are wave-private: same-wave DS ordering covers the RAW
-        // with the writes above
+        const int c = it & 1;
+        const int n = c ^ 1;
+        if (it < 7) {
+          const unsigned nbase =
+              ((it + 1) & 3) * (2 * SUBT) + ((it + 1) >> 2) * 512;
+          TR_READ(fd0[n], b_base + nbase);
+          TR_READ(fd1[n], b_base + nbase + 128);
+          TR_READ(fq0[n], a_base + nbase);
+          TR_READ(fq1[n], a_base + nbase + 128);
+          TR_WAIT4_KEEP(4, fd0[c], fd1[c], fq0[c], fq1[c]);
+        } else {
+          TR_WAIT4_KEEP(0, fd0[c], fd1[c], fq0[c], fq1[c]);
+        }
         dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            pb_afrag(pa, h2, half, l31), tr_join(fd0, fd1),
-            dv_acc[dt], 0, 0, 0);
+            paf[h2], tr_join(fd0[c], fd1[c]), dv_acc[dt], 0, 0, 0);
         dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            pb_afrag(pb, h2, half, l31), tr_join(fq0, fq1),
-            dk_acc[dt], 0, 0, 0);
+            pbf[h2], tr_join(fq0[c], fq1[c]), dk_acc[dt], 0, 0, 0);
       }
     }
+    if (more) write_tiles(&sm.img[cur ^ 1], nxt);
+    // One barrier per tile: img[cur^1] was last read in iteration t-1, and
+    // every wave finished those reads before it passed that barrier.
     __syncthreads();
   }
 
@@ -339,25 +393,34 @@ __device__ inline int st64_addr(int tt, int row, int byte_in_row) {
   return tt * SUBT64 + row * 32 + byte_in_row;
 }
 
+struct Tile64Regs {
+  uint4 k0, k1, v0, v1;
+};
+
 // thread t of 512 stages row r=t>>3, 32-B chunk pair c0=(t&7)*2 of each
-// [64][128] tile (one uint4 pair per tensor)
-__device__ inline void write_tiles64(Tile64* kd, Tile64* vd,
-                                     const bf16* __restrict__ ksrc,
-                                     const bf16* __restrict__ vsrc,
-                                     int64_t ld) {
+// [64][128] tile (one uint4 pair per tensor): global loads and LDS writes
+// are separate steps so the loads can be issued a tile early
+__device__ inline Tile64Regs load_tiles64(const bf16* __restrict__ ksrc,
+                                          const bf16* __restrict__ vsrc,
+                                          int64_t ld) {
   const int t = threadIdx.x;
-  const int r = t >> 3;
-  const int c0 = (t & 7) * 2;
-  const int64_t off = (int64_t)r * ld + c0 * 8;
-  const uint4 k0 = reinterpret_cast<const uint4*>(ksrc + off)[0];
-  const uint4 k1 = reinterpret_cast<const uint4*>(ksrc + off)[1];
-  const uint4 v0 = reinterpret_cast<const uint4*>(vsrc + off)[0];
-  const uint4 v1 = reinterpret_cast<const uint4*>(vsrc + off)[1];
-  const int a0 = st64_addr(c0 >> 1, r, (c0 & 1) * 16);
-  *reinterpret_cast<uint4*>(kd->sub + a0) = k0;
-  *reinterpret_cast<uint4*>(kd->sub + a0 + 16) = k1;
-  *reinterpret_cast<uint4*>(vd->sub + a0) = v0;
-  *reinterpret_cast<uint4*>(vd->sub + a0 + 16) = v1;
+  const int64_t off = (int64_t)(t >> 3) * ld + (t & 7) * 16;
+  Tile64Regs r;
+  r.k0 = reinterpret_cast<const uint4*>(ksrc + off)[0];
+  r.k1 = reinterpret_cast<const uint4*>(ksrc + off)[1];
+  r.v0 = reinterpret_cast<const uint4*>(vsrc + off)[0];
+  r.v1 = reinterpret_cast<const uint4*>(vsrc + off)[1];
+  return r;
+}
+
+__device__ inline void write_tiles64(Tile64* kd, Tile64* vd,
+                                     const Tile64Regs& r) {
+  const int t = threadIdx.x;
+  const int a0 = st64_addr(t & 7, t >> 3, 0);
+  *reinterpret_cast<uint4*>(kd->sub + a0) = r.k0;
+  *reinterpret_cast<uint4*>(kd->sub + a0 + 16) = r.k1;
+  *reinterpret_cast<uint4*>(vd->sub + a0) = r.v0;
+  *reinterpret_cast<uint4*>(vd->sub + a0 + 16) = r.v1;
 }
 
 __device__ inline bf16x8_vec rm64_bfrag(const unsigned char* tile, int tt,
@@ -387,10 +450,12 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
   const int l31 = lane & 31;
-  const int ib = blockIdx.x * FA_WAVES + wave;
+  // causal: the last q block streams the most key tiles — dispatch it first
+  const int bx = causal ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int ib = bx * FA_WAVES + wave;
   const bool active = ib * FA_BLK < S;
   const int nK64 = (S + 63) / 64;
-  const int kv_hi = causal ? (blockIdx.x * FA_WAVES + FA_WAVES) * FA_BLK : S;
+  const int kv_hi = causal ? (bx * FA_WAVES + FA_WAVES) * FA_BLK : S;
   const int T = causal ? (min(kv_hi, S) + 63) / 64 : nK64;
 
   bf16x8_vec qfrag[8], dofrag[8];
@@ -417,12 +482,22 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
   const int64_t kv_ld = bshd ? (int64_t)Hkv * FA_D : FA_D;
   const unsigned tr_off = tr64_lane_off(lane);
 
+  auto tile_regs = [&](int j) -> Tile64Regs {
+    const int64_t off = row_off(b, hkv, j * 64, Hkv, S, bshd);
+    return load_tiles64(k + off, v + off, kv_ld);
+  };
+
+  // prologue: stage key tile 0
+  Tile64Regs pre = tile_regs(0);
+  write_tiles64(&sm.k_img[0], &sm.v_img[0], pre);
+  __syncthreads();
+
   for (int j = 0; j < T; j++) {
     const int cur = j & 1;
-    write_tiles64(&sm.k_img[cur], &sm.v_img[cur],
-                  k + row_off(b, hkv, j * 64, Hkv, S, bshd),
-                  v + row_off(b, hkv, j * 64, Hkv, S, bshd), kv_ld);
-    __syncthreads();
+    // T14 split: key tile j+1's global loads land under tile j's MFMAs.
+    // Wave-uniform guard: the last tile forms no address.
+    const bool more = j + 1 < T;
+    if (more) pre = tile_regs(j + 1);
 
     if (active && !(causal && j * 64 > ib * FA_BLK + FA_BLK - 1)) {
       const unsigned char* kimg = sm.k_img[cur].sub;
@@ -448,14 +523,16 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
         }
 
         const int kg = kb0 + l31;
+        // key minus the lane's first q row: the causal test of C register
+        // rg is one compare against the constant c_row(rg, 0)
+        const int kq = kg - ib * FA_BLK - 4 * half;
 #pragma unroll
         for (int rg = 0; rg < 16; rg++) {
-          const int qg = ib * FA_BLK + c_row(rg, half);
-          const bool valid = !causal || (qg >= kg);
+          const bool valid = !causal || (c_row(rg, 0) >= kq);
           const float p = valid ? __expf(scale * s_acc[rg] - lse_row[rg]) : 0.0f;
           const float ds = p * (dp_acc[rg] - delta_row[rg]) * scale;
-          *reinterpret_cast<bf16*>(pb + pb_addr(c_row(rg, half), l31 * 2)) =
-              __float2bfloat16(ds);
+          *reinterpret_cast<bf16*>(pb + pb_row4_addr(rg >> 2, half, l31) +
+                                   (rg & 3) * 64) = __float2bfloat16(ds);
         }
 
         bf16x8_vec pbf[2];
@@ -489,6 +566,9 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
         }
       }
     }
+    if (more) write_tiles64(&sm.k_img[cur ^ 1], &sm.v_img[cur ^ 1], pre);
+    // One barrier per tile: img[cur^1] was last read in iteration j-1, and
+    // every wave finished those reads before it passed that barrier.
     __syncthreads();
   }
 
