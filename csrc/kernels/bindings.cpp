@@ -1,6 +1,6 @@
 // torch-extension bindings for the CDNA4 kernels (fp8 quantized-collective
-// trio, fused model ops, fused AdamW, DiLoCo outer sync). Tensor-level API consumed by
-// torchft_amd.ops / torchft_amd.quantization.
+// trio, fused model ops, fused AdamW, DiLoCo outer sync, flash attention).
+// Tensor-level API consumed by torchft_amd.ops / torchft_amd.quantization.
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "fa_layout.h"
 #include "kernels.h"
 #include "multi_tensor_host.h"
 
@@ -521,97 +522,140 @@ void diloco_outer_step(const std::vector<at::Tensor>& snapshots,
                         nesterov, (float)alpha, current_stream());
 }
 
-// ---- flash attention backward (appended) -----------------------------------
+// ---- flash attention ----------------------------------------------------------
+
+namespace {
 
 // true when a logical [B,H,S,D] tensor is a transpose view of contiguous
 // [B,S,H,D] storage (the model's projection layout)
-static bool is_bshd(const at::Tensor& t) {
+bool is_bshd(const at::Tensor& t) {
   return t.dim() == 4 && t.stride(3) == 1 && t.stride(1) == t.size(3) &&
          t.stride(2) == t.size(1) * t.size(3) &&
          t.stride(0) == t.size(1) * t.size(2) * t.size(3);
 }
 
-// contiguous in logical [B,H,S,D] order
-static bool is_bhsd(const at::Tensor& t) { return t.is_contiguous(); }
+// The tensors of one attention call and the one rule they are held to. Every
+// logical [B,H,S,128] tensor is bf16 on the device of the first ("q"; dout for
+// fa_delta) with its batch and sequence length; its heads equal q's, or divide
+// them for k / v. Layout: if every tensor is a [B,S,H,D]-backed transpose view
+// the kernels take them as they are (bshd), otherwise each is made contiguous;
+// outputs are allocated in the layout the inputs resolved to.
+struct FaArgs {
+  const char* what;
+  std::vector<at::Tensor> ts;  // q first
+  bool bshd = true;
+
+  FaArgs(const char* what_, const char* name, const at::Tensor& q, int seq_multiple)
+      : what(what_) {
+    TORCH_CHECK(q.is_cuda(), what, ": ", name, " must be a device tensor");
+    check_kind(name, q);
+    TORCH_CHECK(q.size(2) % seq_multiple == 0, what, " requires seq % ", seq_multiple,
+                " == 0");
+    push(q);
+  }
+
+  // dout / out: q's shape
+  void add(const char* name, const at::Tensor& t) {
+    check_kind(name, t);
+    TORCH_CHECK(t.sizes() == q().sizes(), what, ": ", name, " must have the shape of ",
+                "the first tensor, got ", t.sizes(), " against ", q().sizes());
+    push(t);
+  }
+
+  // k and v: one shape, q's batch and sequence, heads dividing q's
+  void add_kv(const at::Tensor& k, const at::Tensor& v) {
+    check_kind("k", k);
+    check_kind("v", v);
+    TORCH_CHECK(k.size(0) == q().size(0) && k.size(2) == q().size(2), what,
+                ": k must have q's batch and sequence length, got ", k.sizes(), " against ",
+                q().sizes());
+    TORCH_CHECK(k.size(1) > 0 && q().size(1) % k.size(1) == 0,
+                "Hq must be a multiple of Hkv (k has ", k.size(1), " heads)");
+    TORCH_CHECK(v.sizes() == k.sizes(), what, ": v must have k's shape, got ", v.sizes(),
+                " against ", k.sizes());
+    push(k);
+    push(v);
+  }
+
+  // lse / delta: B*Hq*S row statistics on q's device, as dense fp32
+  at::Tensor stat(const char* name, const at::Tensor& t) const {
+    TORCH_CHECK(t.device() == q().device(), what, ": ", name, " must be on q's device");
+    TORCH_CHECK(t.numel() == q().size(0) * q().size(1) * q().size(2), what, ": ", name,
+                " shape mismatch (", t.numel(), " elements, need B*Hq*S)");
+    return t.contiguous().to(at::kFloat);
+  }
+
+  const at::Tensor& q() const { return ts[0]; }
+  // tensor i as the kernels read it
+  at::Tensor in(size_t i) const { return bshd ? ts[i] : ts[i].contiguous(); }
+  // an uninitialized tensor of ts[i]'s logical shape in the resolved layout:
+  // with bshd a transpose view of a [B,S,H,D] buffer, so a later
+  // .transpose(1, 2).reshape() in the model is free and gradients reach the
+  // projections without a copy
+  at::Tensor out_like(size_t i) const {
+    const at::Tensor& t = ts[i];
+    if (!bshd) return at::empty(t.sizes(), t.options());
+    return at::empty({t.size(0), t.size(2), t.size(1), t.size(3)}, t.options())
+        .transpose(1, 2);
+  }
+
+ private:
+  void check_kind(const char* name, const at::Tensor& t) const {
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 4, what, ": ", name,
+                " must be a 4-D bf16 tensor, got ", t.dim(), "-D ", t.scalar_type());
+    TORCH_CHECK(ts.empty() || t.device() == q().device(), what, ": ", name,
+                " must be on the device of the first tensor");
+    TORCH_CHECK(t.size(3) == tft::kFaD, what, " supports head_dim=128 only (", name,
+                " has ", t.size(3), ")");
+  }
+  void push(const at::Tensor& t) {
+    bshd = bshd && is_bshd(t);
+    ts.push_back(t);
+  }
+};
+
+}  // namespace
 
 at::Tensor fa_delta(at::Tensor dout, at::Tensor out) {
-  TORCH_CHECK(dout.is_cuda() && dout.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(dout.size(-1) == 128);
-  const bool bshd = is_bshd(dout) && is_bshd(out);
-  auto dc = bshd ? dout : dout.contiguous();
-  auto oc = bshd ? out : out.contiguous();
-  const int64_t rows = dc.numel() / 128;
+  FaArgs a("fa_delta", "dout", dout, /*seq_multiple=*/1);
+  a.add("out", out);
+  auto dc = a.in(0), oc = a.in(1);
   // delta is always dense [B, Hq, S]
   auto delta = at::empty({dout.size(0), dout.size(1), dout.size(2)},
                          dout.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
   tft::launch_fa_delta(dc.data_ptr(), oc.data_ptr(), delta.data_ptr<float>(),
-                       rows, (int)dout.size(1), (int)dout.size(2), bshd,
-                       (tft_stream)stream);
+                       dc.numel() / tft::kFaD, (int)dout.size(1), (int)dout.size(2),
+                       a.bshd, current_stream());
   return delta;
 }
 
 std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                double scale, bool causal) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.dim() == 4);
-  TORCH_CHECK(q.size(3) == 128, "fa_fwd supports head_dim=128 only");
-  TORCH_CHECK(q.size(2) % 256 == 0, "fa_fwd requires seq % 256 == 0");
-  const int64_t B = q.size(0), Hq = q.size(1), S = q.size(2);
-  const int64_t Hkv = k.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "Hq must be a multiple of Hkv");
-  const bool bshd = is_bshd(q) && is_bshd(k) && is_bshd(v);
-  auto qc = bshd ? q : q.contiguous();
-  auto kc = bshd ? k : k.contiguous();
-  auto vc = bshd ? v : v.contiguous();
-  // out matches the input layout: with bshd storage the logical [B,Hq,S,D]
-  // result is a transpose view of a [B,S,Hq,D] buffer (so a later
-  // .transpose(1,2).reshape() in the model is free)
-  auto out = bshd
-                 ? at::empty({B, S, Hq, (int64_t)128}, q.options()).transpose(1, 2)
-                 : at::empty_like(qc);
-  auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                     out.data_ptr(), lse.data_ptr<float>(), (int)B, (int)Hq,
-                     (int)Hkv, (int)S, (float)scale, causal, bshd,
-                     (tft_stream)stream);
+  FaArgs a("fa_fwd", "q", q, /*seq_multiple=*/256);
+  a.add_kv(k, v);
+  auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
+  auto out = a.out_like(0);
+  auto lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
+  tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
+                     lse.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)k.size(1),
+                     (int)q.size(2), (float)scale, causal, a.bshd, current_stream());
   return {out, lse};
 }
 
 std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                at::Tensor dout, at::Tensor lse, at::Tensor delta,
                                double scale, bool causal) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16 && q.dim() == 4);
-  TORCH_CHECK(q.size(3) == 128, "fa_bwd supports head_dim=128 only");
-  TORCH_CHECK(q.size(2) % 128 == 0, "fa_bwd requires seq % 128 == 0");
-  const int64_t B = q.size(0), Hq = q.size(1), S = q.size(2);
-  const int64_t Hkv = k.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "Hq must be a multiple of Hkv");
-  const bool bshd = is_bshd(q) && is_bshd(k) && is_bshd(v) && is_bshd(dout);
-  auto qc = bshd ? q : q.contiguous();
-  auto kc = bshd ? k : k.contiguous();
-  auto vc = bshd ? v : v.contiguous();
-  auto doc = bshd ? dout : dout.contiguous();
-  auto lsec = lse.contiguous().to(at::kFloat);
-  auto deltac = delta.contiguous().to(at::kFloat);
-  TORCH_CHECK(lsec.numel() == B * Hq * S, "lse shape mismatch");
-  // gradients come back in the inputs' layout (bshd: transpose views of
-  // [B,S,H,D] buffers) so the autograd graph above never copies
-  auto mk = [&](const at::Tensor& like) {
-    if (!bshd) return at::empty_like(like.contiguous());
-    return at::empty({like.size(0), like.size(2), like.size(1), like.size(3)},
-                     like.options())
-        .transpose(1, 2);
-  };
-  auto dq = mk(q);
-  auto dk = mk(k);
-  auto dv = mk(v);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
+  FaArgs a("fa_bwd", "q", q, /*seq_multiple=*/128);
+  a.add_kv(k, v);
+  a.add("dout", dout);
+  auto lsec = a.stat("lse", lse), deltac = a.stat("delta", delta);
+  auto qc = a.in(0), kc = a.in(1), vc = a.in(2), doc = a.in(3);
+  auto dq = a.out_like(0), dk = a.out_like(1), dv = a.out_like(2);
   tft::launch_fa_bwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), doc.data_ptr(),
-                     lsec.data_ptr<float>(), deltac.data_ptr<float>(),
-                     dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), (int)B,
-                     (int)Hq, (int)Hkv, (int)S, (float)scale, causal, bshd,
-                     (tft_stream)stream);
+                     lsec.data_ptr<float>(), deltac.data_ptr<float>(), dq.data_ptr(),
+                     dk.data_ptr(), dv.data_ptr(), (int)q.size(0), (int)q.size(1),
+                     (int)k.size(1), (int)q.size(2), (float)scale, causal, a.bshd,
+                     current_stream());
   return {dq, dk, dv};
 }
 

@@ -13,17 +13,15 @@
 // fp32 accumulators in the unified VGPR/AGPR file.
 //
 // Schedule (v3): the staged tiles live in ONE subtiled row-major LDS image
-// ([8 d-subtiles][32 rows][16 cols], 1040-B subtile stride) serving BOTH
-// fragment orientations: contiguous ds_read_b128 for the S/dP chains and
-// hardware-transpose ds_read_b64_tr_b16 for the dV/dK/dQ chains. This
-// removes v2's separate transposed images and their 32-per-thread b16
-// scatter writes (the worst LDS citizen in the v2 profile). tr_b16
-// semantics verified by csrc/kernels/tr16_probe.hip on gfx950: with
-// lane-linear 8-B addresses over a contiguous [4][16] bf16 block per
-// 16-lane group, lane l receives column (l&15), elements j=0..3 = rows.
-// The 1040-B subtile stride (65 x 16 B) makes the 8 staging ds_write_b128
-// of a wave's lane group land on 8 distinct bank quads (1024 would be
-// 8-way conflicted).
+// (Tile<ROWS> of fa_layout.h: [8 d-subtiles][ROWS rows][16 cols], subtile
+// stride 65 * ROWS/2 bytes) serving BOTH fragment orientations: contiguous
+// ds_read_b128 for the S/dP chains and hardware-transpose
+// ds_read_b64_tr_b16 for the dV/dK/dQ chains. This removes v2's separate
+// transposed images and their 32-per-thread b16 scatter writes (the worst
+// LDS citizen in the v2 profile). tr_b16 semantics verified by
+// csrc/kernels/tr16_probe.hip on gfx950: with lane-linear 8-B addresses
+// over a contiguous [4][16] bf16 block per 16-lane group, lane l receives
+// column (l&15), elements j=0..3 = rows.
 //
 // Pipeline (v4): both tile streams are software-pipelined one tile deep
 // (T14 async-STAGE split). A prologue stages tile 0; each iteration issues
@@ -38,148 +36,31 @@
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
 
-#include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
+#include "fa_tile.h"
 
 namespace torchft_amd {
 
-using bf16 = __hip_bfloat16;
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8_vec;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
-
-#define FA_D 128
-#define FA_BLK 32
-#define FA_WAVES 8
-#define FA_THREADS 512
-#define SUBT 1040  // subtile stride: 32 rows x 32 B + 16-B pad (see header)
-
-// ---- LDS image geometry ---------------------------------------------------
-// One 32x128 bf16 tile = 8 subtiles of [32 rows][16 cols], each row-major
-// and element-contiguous (tr_b16 needs its [4][16] blocks contiguous).
-struct Tile {
-  __align__(16) unsigned char sub[8 * SUBT];
-};
-
+// dkdv streams 32-row Q / dO tiles (geometry and staging: fa_layout.h)
 struct ImageSet {
-  Tile a;  // Q (dkdv) / K (dq)
-  Tile b;  // dO (dkdv) / V (dq)
+  Tile<32> a;  // Q
+  Tile<32> b;  // dO
 };
-
-// byte address of element [row][col16] in subtile tt
-__device__ inline int st_addr(int tt, int row, int byte_in_row) {
-  return tt * SUBT + row * 32 + byte_in_row;
-}
 
 struct SmemFA {
-  ImageSet img[2];                                    // double buffer
-  __align__(16) unsigned char pa[FA_WAVES][32 * 64];  // P transpose bufs
-  __align__(16) unsigned char pb[FA_WAVES][32 * 64];  // dS transpose bufs
+  ImageSet img[2];                                  // double buffer
+  alignas(16) unsigned char pa[kFaWaves][32 * 64];  // P transpose bufs
+  alignas(16) unsigned char pb[kFaWaves][32 * 64];  // dS transpose bufs
   // per-wave V operand tile (8 slots) + the last two K k-slices (2 slots)
   // in A-fragment order (dkdv kernel only): [wave][slot][lane][8 bf16] =
   // one b128 per (slot, lane). The first six K k-slices live in VGPRs —
   // all eight would push the allocator over the 256-VGPR spill cliff.
-  __align__(16) unsigned char v_ops[FA_WAVES][10 * 64 * 16];
+  alignas(16) unsigned char v_ops[kFaWaves][10 * 64 * 16];
 };
-
-struct TileRegs {
-  uint4 a, b;
-};
-
-// issue the global loads for one (tileA, tileB) pair; thread t of 512 owns
-// row q=t>>4 and 16-B chunk c=t&15 (8 d columns) of each 32x128 tile.
-// ld = elements between consecutive sequence rows (layout-dependent).
-__device__ inline TileRegs load_tiles(const bf16* __restrict__ srcA,
-                                      const bf16* __restrict__ srcB,
-                                      int64_t ld) {
-  const int t = threadIdx.x;
-  const int64_t off = (int64_t)(t >> 4) * ld + (t & 15) * 8;
-  TileRegs r;
-  r.a = reinterpret_cast<const uint4*>(srcA + off)[0];
-  r.b = reinterpret_cast<const uint4*>(srcB + off)[0];
-  return r;
-}
-
-__device__ inline void write_tiles(ImageSet* img, const TileRegs& r) {
-  const int t = threadIdx.x;
-  const int addr = st_addr((t & 15) >> 1, t >> 4, (t & 1) * 16);
-  *reinterpret_cast<uint4*>(img->a.sub + addr) = r.a;
-  *reinterpret_cast<uint4*>(img->b.sub + addr) = r.b;
-}
-
-// B-fragment for the S/dP chains (k-dim = d): contiguous b128 read.
-// k-slice tt covers d = tt*16 + half*8 .. +8 of row l31.
-__device__ inline bf16x8_vec rm_bfrag(const unsigned char* tile, int tt, int half,
-                                      int l31) {
-  return *reinterpret_cast<const bf16x8_vec*>(tile + st_addr(tt, l31, half * 16));
-}
-
-// pa/pb A-fragment read (row=l31, 8 consecutive elements at h2*16+half*8)
-__device__ inline int row_swz(int row, int byte_off) {
-  return byte_off ^ ((((row >> 2) ^ (row >> 4)) & 3) << 4);
-}
-__device__ inline int pb_addr(int row, int byte_off) {
-  return row * 64 + row_swz(row, byte_off);  // 32 x 64 B
-}
-__device__ inline bf16x8_vec pb_afrag(const unsigned char* pb, int h2, int half,
-                                      int l31) {
-  return *reinterpret_cast<const bf16x8_vec*>(pb + pb_addr(l31, h2 * 32 + half * 16));
-}
-__device__ inline int c_row(int reg, int half) {
-  return (reg & 3) + 8 * (reg >> 2) + 4 * half;
-}
-// pa/pb address of a lane's C element (row c_row(4*r4, half), col l31).
-// The four rows c_row(4*r4 + r, half), r = 0..3, share one swizzle key, so
-// they sit at +64*r: 4 address registers serve the 16 stores, not 16.
-__device__ inline int pb_row4_addr(int r4, int half, int l31) {
-  return pb_addr(8 * r4 + 4 * half, l31 * 2);
-}
-
-// per-lane invariant part of every tr_b16 address (see header):
-//   sub parity (l>>4)&1, k-half row offset (l>>5)*8 rows, chunk (l&15)*8 B
-__device__ inline unsigned tr_lane_off(int lane) {
-  return ((lane >> 4) & 1) * SUBT + ((lane >> 5) * 8) * 32 + (lane & 15) * 8;
-}
-
-// one hardware-transpose read: 4 bf16 = column (l&15), rows j=0..3 of the
-// [4][16] block at (per-lane) byte address `addr` into the LDS image
-#define TR_READ(dst, addr) \
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(addr))
-
-// Counted wait: allow N newer LDS ops to stay in flight, and tie the four
-// registers the following MFMAs consume so they cannot be scheduled above
-// the wait (explicit dataflow — "memory" alone would not order
-// register-only MFMAs past an asm wait, §5.4 rule 18).
-#define TR_WAIT4_KEEP(N, r0, r1, r2, r3)              \
-  asm volatile("s_waitcnt lgkmcnt(" #N ")"            \
-               : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3))
-#define TR_WAIT2_KEEP(N, r0, r1) \
-  asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(r0), "+v"(r1))
-
-// element offset of sequence row s of head (b,h): bshd=1 means the
-// storage is [B,S,H,D] (the model's projection layout, seen through a
-// transpose view) — supporting it natively removes every layout copy the
-// autograd path would otherwise pay.
-__device__ inline int64_t row_off(int b, int h, int s, int H, int S, int bshd) {
-  return bshd ? (((int64_t)b * S + s) * H + h) * FA_D
-              : (((int64_t)b * H + h) * S + s) * FA_D;
-}
-
-__device__ inline bf16x8_vec tr_join(unsigned long long lo, unsigned long long hi) {
-  union {
-    struct {
-      unsigned long long lo, hi;
-    } u;
-    bf16x8_vec v;
-  } c;
-  c.u.lo = lo;
-  c.u.hi = hi;
-  return c.v;
-}
 
 // ---- kernel 1: dK/dV ------------------------------------------------------
-__global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
+__global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
@@ -193,10 +74,10 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
   const int l31 = lane & 31;
-  const int jb = blockIdx.x * FA_WAVES + wave;
-  const bool active = jb * FA_BLK < S;
-  const int nQ = S / FA_BLK;
-  const int i_min = causal ? blockIdx.x * FA_WAVES : 0;
+  const int jb = blockIdx.x * kFaWaves + wave;
+  const bool active = jb * kFaBlk < S;
+  const int nQ = S / kFaBlk;
+  const int i_min = causal ? blockIdx.x * kFaWaves : 0;
   const int nI = nQ - i_min;
   const int T = G * nI;  // flattened (g, i) iteration count
 
@@ -205,7 +86,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
   unsigned char* vops = sm.v_ops[wave];
   bf16x8_vec kfrag[6];
   if (active) {
-    const int64_t kv_off = row_off(b, hkv, jb * FA_BLK + l31, Hkv, S, bshd);
+    const int64_t kv_off = row_off(b, hkv, jb * kFaBlk + l31, Hkv, S, bshd);
 #pragma unroll
     for (int t = 0; t < 8; t++) {
       const bf16x8_vec kv =
@@ -223,23 +104,23 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
   f32x16 dk_acc[4] = {};
   f32x16 dv_acc[4] = {};
 
-  const int64_t q_ld = bshd ? (int64_t)Hq * FA_D : FA_D;  // seq-row stride
+  const int64_t q_ld = bshd ? (int64_t)Hq * kFaD : kFaD;  // seq-row stride
   const float* lse_base = lse + ((int64_t)b * Hq + hkv * G) * S;
   const float* delta_base = delta + ((int64_t)b * Hq + hkv * G) * S;
 
   auto tile_src = [&](int t, const bf16* base) -> const bf16* {
     const int g = t / nI;
     const int i = i_min + t % nI;
-    return base + row_off(b, hkv * G + g, i * FA_BLK, Hq, S, bshd);
+    return base + row_off(b, hkv * G + g, i * kFaBlk, Hq, S, bshd);
   };
 
-  const unsigned tr_off = tr_lane_off(lane);
+  const unsigned tr_off = Tile<32>::tr_lane_off(lane);
 
   // prologue: stage tile 0 and its row statistics
-  TileRegs nxt = load_tiles(tile_src(0, q), tile_src(0, dout), q_ld);
-  float lse_n = lse_base[i_min * FA_BLK + l31];
-  float delta_n = delta_base[i_min * FA_BLK + l31];
-  write_tiles(&sm.img[0], nxt);
+  TileRegs<32> nxt = load_tiles<32>(tile_src(0, q), tile_src(0, dout), q_ld);
+  float lse_n = lse_base[i_min * kFaBlk + l31];
+  float delta_n = delta_base[i_min * kFaBlk + l31];
+  write_tiles(&sm.img[0].a, &sm.img[0].b, nxt);
   __syncthreads();
 
   for (int t = 0; t < T; t++) {
@@ -267,16 +148,16 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
                    : *reinterpret_cast<const bf16x8_vec*>(
                          vops + ((tt + 2) * 64 + lane) * 16);
         s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            kf, rm_bfrag(img->a.sub, tt, half, l31), s_acc, 0, 0, 0);
+            kf, rm_frag<32>(img->a.sub, tt, l31, half), s_acc, 0, 0, 0);
         dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            vf, rm_bfrag(img->b.sub, tt, half, l31), dp_acc, 0, 0, 0);
+            vf, rm_frag<32>(img->b.sub, tt, l31, half), dp_acc, 0, 0, 0);
       }
 
       unsigned char* pa = sm.pa[wave];
       unsigned char* pb = sm.pb[wave];
       // q row minus the lane's first key row: the causal test of C register
       // rg is one compare against the constant c_row(rg, 0)
-      const int qk = (i - jb) * FA_BLK + l31 - 4 * half;
+      const int qk = (i - jb) * kFaBlk + l31 - 4 * half;
 #pragma unroll
       for (int rg = 0; rg < 16; rg++) {
         const bool valid = !causal || (qk >= c_row(rg, 0));
@@ -295,8 +176,8 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
     // forms no address.
     if (more) {
       const int64_t st = (int64_t)((t + 1) / nI) * S +
-                         (i_min + (t + 1) % nI) * FA_BLK + l31;
-      nxt = load_tiles(tile_src(t + 1, q), tile_src(t + 1, dout), q_ld);
+                         (i_min + (t + 1) % nI) * kFaBlk + l31;
+      nxt = load_tiles<32>(tile_src(t + 1, q), tile_src(t + 1, dout), q_ld);
       lse_n = lse_base[st];
       delta_n = delta_base[st];
     }
@@ -337,8 +218,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
         const int c = it & 1;
         const int n = c ^ 1;
         if (it < 7) {
-          const unsigned nbase =
-              ((it + 1) & 3) * (2 * SUBT) + ((it + 1) >> 2) * 512;
+          const unsigned nbase = Tile<32>::tr_step_off((it + 1) & 3, (it + 1) >> 2);
           TR_READ(fd0[n], b_base + nbase);
           TR_READ(fd1[n], b_base + nbase + 128);
           TR_READ(fq0[n], a_base + nbase);
@@ -353,7 +233,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
             pbf[h2], tr_join(fq0[c], fq1[c]), dk_acc[dt], 0, 0, 0);
       }
     }
-    if (more) write_tiles(&sm.img[cur ^ 1], nxt);
+    if (more) write_tiles(&sm.img[cur ^ 1].a, &sm.img[cur ^ 1].b, nxt);
     // One barrier per tile: img[cur^1] was last read in iteration t-1, and
     // every wave finished those reads before it passed that barrier.
     __syncthreads();
@@ -365,7 +245,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
 #pragma unroll
     for (int rg = 0; rg < 16; rg++) {
       const int key = c_row(rg, half);
-      const int64_t row = row_off(b, hkv, jb * FA_BLK + key, Hkv, S, bshd);
+      const int64_t row = row_off(b, hkv, jb * kFaBlk + key, Hkv, S, bshd);
       const int d = dt * 32 + l31;
       dk[row + d] = __float2bfloat16(dk_acc[dt][rg]);
       dv[row + d] = __float2bfloat16(dv_acc[dt][rg]);
@@ -373,69 +253,17 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dkdv_kernel(
   }
 }
 
-// ---- dq-kernel 64-key tile geometry ---------------------------------------
-// [8 d-subtiles][64 rows][16 cols] with a 16-B pad: staging a 64-key K/V
-// tile per barrier pair halves the per-MFMA staging/barrier overhead vs
-// the 32-key tiles the dkdv kernel uses for its Q/dO stream.
-#define SUBT64 2080
-
-struct Tile64 {
-  __align__(16) unsigned char sub[8 * SUBT64];
-};
-
+// ---- dq-kernel 64-key tiles ------------------------------------------------
+// Staging a 64-key K/V tile per barrier halves the per-MFMA staging/barrier
+// overhead vs the 32-key tiles the dkdv kernel uses for its Q/dO stream.
 struct SmemDq {
-  Tile64 k_img[2];
-  Tile64 v_img[2];
-  __align__(16) unsigned char pb[FA_WAVES][32 * 64];
+  Tile<64> k_img[2];
+  Tile<64> v_img[2];
+  alignas(16) unsigned char pb[kFaWaves][32 * 64];
 };
-
-__device__ inline int st64_addr(int tt, int row, int byte_in_row) {
-  return tt * SUBT64 + row * 32 + byte_in_row;
-}
-
-struct Tile64Regs {
-  uint4 k0, k1, v0, v1;
-};
-
-// thread t of 512 stages row r=t>>3, 32-B chunk pair c0=(t&7)*2 of each
-// [64][128] tile (one uint4 pair per tensor): global loads and LDS writes
-// are separate steps so the loads can be issued a tile early
-__device__ inline Tile64Regs load_tiles64(const bf16* __restrict__ ksrc,
-                                          const bf16* __restrict__ vsrc,
-                                          int64_t ld) {
-  const int t = threadIdx.x;
-  const int64_t off = (int64_t)(t >> 3) * ld + (t & 7) * 16;
-  Tile64Regs r;
-  r.k0 = reinterpret_cast<const uint4*>(ksrc + off)[0];
-  r.k1 = reinterpret_cast<const uint4*>(ksrc + off)[1];
-  r.v0 = reinterpret_cast<const uint4*>(vsrc + off)[0];
-  r.v1 = reinterpret_cast<const uint4*>(vsrc + off)[1];
-  return r;
-}
-
-__device__ inline void write_tiles64(Tile64* kd, Tile64* vd,
-                                     const Tile64Regs& r) {
-  const int t = threadIdx.x;
-  const int a0 = st64_addr(t & 7, t >> 3, 0);
-  *reinterpret_cast<uint4*>(kd->sub + a0) = r.k0;
-  *reinterpret_cast<uint4*>(kd->sub + a0 + 16) = r.k1;
-  *reinterpret_cast<uint4*>(vd->sub + a0) = r.v0;
-  *reinterpret_cast<uint4*>(vd->sub + a0 + 16) = r.v1;
-}
-
-__device__ inline bf16x8_vec rm64_bfrag(const unsigned char* tile, int tt,
-                                        int row, int half) {
-  return *reinterpret_cast<const bf16x8_vec*>(
-      tile + st64_addr(tt, row, half * 16));
-}
-
-// tr_b16 lane invariant in the 64-row subtiles
-__device__ inline unsigned tr64_lane_off(int lane) {
-  return ((lane >> 4) & 1) * SUBT64 + ((lane >> 5) * 8) * 32 + (lane & 15) * 8;
-}
 
 // ---- kernel 2: dQ ---------------------------------------------------------
-__global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
+__global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
@@ -452,16 +280,16 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
   const int l31 = lane & 31;
   // causal: the last q block streams the most key tiles — dispatch it first
   const int bx = causal ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
-  const int ib = bx * FA_WAVES + wave;
-  const bool active = ib * FA_BLK < S;
+  const int ib = bx * kFaWaves + wave;
+  const bool active = ib * kFaBlk < S;
   const int nK64 = (S + 63) / 64;
-  const int kv_hi = causal ? (bx * FA_WAVES + FA_WAVES) * FA_BLK : S;
+  const int kv_hi = causal ? (bx * kFaWaves + kFaWaves) * kFaBlk : S;
   const int T = causal ? (min(kv_hi, S) + 63) / 64 : nK64;
 
   bf16x8_vec qfrag[8], dofrag[8];
   float lse_row[16], delta_row[16];
   if (active) {
-    const int64_t q_off = row_off(b, hq, ib * FA_BLK + l31, Hq, S, bshd);
+    const int64_t q_off = row_off(b, hq, ib * kFaBlk + l31, Hq, S, bshd);
 #pragma unroll
     for (int t = 0; t < 8; t++) {
       qfrag[t] = *reinterpret_cast<const bf16x8_vec*>(q + q_off + t * 16 + half * 8);
@@ -471,7 +299,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
     const float* delta_head = delta + ((int64_t)b * Hq + hq) * S;
 #pragma unroll
     for (int rg = 0; rg < 16; rg++) {
-      const int row = ib * FA_BLK + c_row(rg, half);
+      const int row = ib * kFaBlk + c_row(rg, half);
       lse_row[rg] = lse_head[row];
       delta_row[rg] = delta_head[row];
     }
@@ -479,17 +307,17 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
 
   f32x16 dq_acc[4] = {};
 
-  const int64_t kv_ld = bshd ? (int64_t)Hkv * FA_D : FA_D;
-  const unsigned tr_off = tr64_lane_off(lane);
+  const int64_t kv_ld = bshd ? (int64_t)Hkv * kFaD : kFaD;
+  const unsigned tr_off = Tile<64>::tr_lane_off(lane);
 
-  auto tile_regs = [&](int j) -> Tile64Regs {
+  auto tile_regs = [&](int j) -> TileRegs<64> {
     const int64_t off = row_off(b, hkv, j * 64, Hkv, S, bshd);
-    return load_tiles64(k + off, v + off, kv_ld);
+    return load_tiles<64>(k + off, v + off, kv_ld);
   };
 
   // prologue: stage key tile 0
-  Tile64Regs pre = tile_regs(0);
-  write_tiles64(&sm.k_img[0], &sm.v_img[0], pre);
+  TileRegs<64> pre = tile_regs(0);
+  write_tiles(&sm.k_img[0], &sm.v_img[0], pre);
   __syncthreads();
 
   for (int j = 0; j < T; j++) {
@@ -499,7 +327,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
     const bool more = j + 1 < T;
     if (more) pre = tile_regs(j + 1);
 
-    if (active && !(causal && j * 64 > ib * FA_BLK + FA_BLK - 1)) {
+    if (active && !(causal && j * 64 > ib * kFaBlk + kFaBlk - 1)) {
       const unsigned char* kimg = sm.k_img[cur].sub;
       const unsigned char* vimg = sm.v_img[cur].sub;
       const unsigned a_base = (unsigned)(uintptr_t)kimg + tr_off;
@@ -508,24 +336,22 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
 #pragma unroll
       for (int s = 0; s < 2; s++) {  // two 32-key halves per staged tile
         const int kb0 = j * 64 + s * 32;
-        if (causal && kb0 > ib * FA_BLK + FA_BLK - 1) break;
+        if (causal && kb0 > ib * kFaBlk + kFaBlk - 1) break;
 
         f32x16 s_acc = {};
         f32x16 dp_acc = {};
 #pragma unroll
         for (int tt = 0; tt < 8; tt++) {
           s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              qfrag[tt], rm64_bfrag(kimg, tt, s * 32 + l31, half), s_acc, 0, 0,
-              0);
+              qfrag[tt], rm_frag<64>(kimg, tt, s * 32 + l31, half), s_acc, 0, 0, 0);
           dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              dofrag[tt], rm64_bfrag(vimg, tt, s * 32 + l31, half), dp_acc, 0,
-              0, 0);
+              dofrag[tt], rm_frag<64>(vimg, tt, s * 32 + l31, half), dp_acc, 0, 0, 0);
         }
 
         const int kg = kb0 + l31;
         // key minus the lane's first q row: the causal test of C register
         // rg is one compare against the constant c_row(rg, 0)
-        const int kq = kg - ib * FA_BLK - 4 * half;
+        const int kq = kg - ib * kFaBlk - 4 * half;
 #pragma unroll
         for (int rg = 0; rg < 16; rg++) {
           const bool valid = !causal || (c_row(rg, 0) >= kq);
@@ -552,9 +378,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
           const int cur2 = it & 1;
           const int nxt = cur2 ^ 1;
           if (it < 7) {
-            const int it2 = it + 1;
-            const unsigned nbase =
-                (it2 & 3) * (2 * SUBT64) + (it2 >> 2) * 512;
+            const unsigned nbase = Tile<64>::tr_step_off((it + 1) & 3, (it + 1) >> 2);
             TR_READ(fk0[nxt], s_base + nbase);
             TR_READ(fk1[nxt], s_base + nbase + 128);
             TR_WAIT2_KEEP(2, fk0[cur2], fk1[cur2]);
@@ -566,7 +390,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
         }
       }
     }
-    if (more) write_tiles64(&sm.k_img[cur ^ 1], &sm.v_img[cur ^ 1], pre);
+    if (more) write_tiles(&sm.k_img[cur ^ 1], &sm.v_img[cur ^ 1], pre);
     // One barrier per tile: img[cur^1] was last read in iteration j-1, and
     // every wave finished those reads before it passed that barrier.
     __syncthreads();
@@ -577,7 +401,7 @@ __global__ __launch_bounds__(FA_THREADS, 1) void fa_bwd_dq_kernel(
   for (int dt = 0; dt < 4; dt++) {
 #pragma unroll
     for (int rg = 0; rg < 16; rg++) {
-      dq[row_off(b, hq, ib * FA_BLK + c_row(rg, half), Hq, S, bshd) + dt * 32 +
+      dq[row_off(b, hq, ib * kFaBlk + c_row(rg, half), Hq, S, bshd) + dt * 32 +
          l31] = __float2bfloat16(dq_acc[dt][rg]);
     }
   }
@@ -606,9 +430,9 @@ __global__ void fa_delta_kernel(const bf16* __restrict__ dout,
   }
   // 64 lanes x 2 contiguous bf16 cover the D=128 row
   const __hip_bfloat162 d2 =
-      *reinterpret_cast<const __hip_bfloat162*>(dout + row * FA_D + lane * 2);
+      *reinterpret_cast<const __hip_bfloat162*>(dout + row * kFaD + lane * 2);
   const __hip_bfloat162 o2 =
-      *reinterpret_cast<const __hip_bfloat162*>(o + row * FA_D + lane * 2);
+      *reinterpret_cast<const __hip_bfloat162*>(o + row * kFaD + lane * 2);
   float2 df = __bfloat1622float2(d2);
   float2 of = __bfloat1622float2(o2);
   float v = df.x * of.x + df.y * of.y;
@@ -633,12 +457,12 @@ void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout
                    const float* lse, const float* delta, void* dq, void* dk,
                    void* dv, int B, int Hq, int Hkv, int S, float scale,
                    bool causal, bool bshd, hipStream_t stream) {
-  const int nblk = (S + FA_BLK * FA_WAVES - 1) / (FA_BLK * FA_WAVES);
-  hipLaunchKernelGGL(fa_bwd_dkdv_kernel, dim3(nblk, B * Hkv), dim3(FA_THREADS), 0,
+  const int nblk = (S + kFaBlk * kFaWaves - 1) / (kFaBlk * kFaWaves);
+  hipLaunchKernelGGL(fa_bwd_dkdv_kernel, dim3(nblk, B * Hkv), dim3(kFaThreads), 0,
                      stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, B, Hq,
                      Hkv, S, scale, causal ? 1 : 0, bshd ? 1 : 0);
-  hipLaunchKernelGGL(fa_bwd_dq_kernel, dim3(nblk, B * Hq), dim3(FA_THREADS), 0,
+  hipLaunchKernelGGL(fa_bwd_dq_kernel, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
                      stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq, Hkv, S,
                      scale, causal ? 1 : 0, bshd ? 1 : 0);

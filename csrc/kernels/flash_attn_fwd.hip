@@ -31,114 +31,33 @@
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
 
-#include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
+#include "fa_tile.h"
 
 namespace torchft_amd {
 
-using bf16 = __hip_bfloat16;
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8_vec;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
+constexpr int kFwdKvBlk = 64;       // keys per staged K/V tile
+constexpr float kFwdThr = 11.54f;   // defer-max threshold: 8 nats in log2 units
+constexpr float kLog2e = 1.44269504089f;
 
-#define FWD_D 128
-#define FWD_QBLK 32
-#define FWD_KVBLK 64
-#define FWD_WAVES 8
-#define FWD_THREADS 512
-// V/K subtile: [64 rows][16 cols] bf16 + 16-B pad -> stride 2080:
-// 2080/4 = 520 ≡ 8 (mod 32): the 8 staging ds_write_b128 of a lane group
-// hit 4 distinct bank quads (2-way); ≡ 8 (mod 64) keeps adjacent-subtile
-// tr blocks mostly disjoint.
-#define FSUBT 2080
-#define FWD_THR 11.54f  // defer-max threshold: 8 nats in log2 units
-#define LOG2E 1.44269504089f
-
-struct FwdTile {
-  __align__(16) unsigned char sub[8 * FSUBT];
-};
-
+// K/V tiles are Tile<64> (fa_layout.h), staged by the shared T14 stream of
+// fa_tile.h: the loads issue an iteration EARLY (under the previous tile's
+// MFMA phase, hiding the HBM latency); the writes land after the barrier
+// that frees the buffer.
 struct SmemFwd {
-  FwdTile k_img[2];
-  FwdTile v_img[2];
-  __align__(16) float bcast[FWD_WAVES][32];  // alpha / 1/l broadcasts
+  Tile<64> k_img[2];
+  Tile<64> v_img[2];
+  alignas(16) float bcast[kFaWaves][32];  // alpha / 1/l broadcasts
 };
 
-__device__ inline int fst_addr(int tt, int row, int byte_in_row) {
-  return tt * FSUBT + row * 32 + byte_in_row;
-}
-
-// T14 async-STAGE split: thread t of 512 owns rows r=t>>3, 32-B chunk
-// pair c0=(t&7)*2 of each [64][128] bf16 tile. The loads issue an
-// iteration EARLY (under the previous tile's MFMA phase, hiding the HBM
-// latency); the writes land after the barrier that frees the buffer.
-struct KvRegs {
-  uint4 k0, k1, v0, v1;
-};
-
-__device__ inline KvRegs load_kv(const bf16* __restrict__ ksrc,
-                                 const bf16* __restrict__ vsrc, int64_t ld) {
-  const int t = threadIdx.x;
-  const int64_t off = (int64_t)(t >> 3) * ld + ((t & 7) * 2) * 8;
-  KvRegs r;
-  r.k0 = reinterpret_cast<const uint4*>(ksrc + off)[0];
-  r.k1 = reinterpret_cast<const uint4*>(ksrc + off)[1];
-  r.v0 = reinterpret_cast<const uint4*>(vsrc + off)[0];
-  r.v1 = reinterpret_cast<const uint4*>(vsrc + off)[1];
-  return r;
-}
-
-__device__ inline void write_kv(FwdTile* kd, FwdTile* vd, const KvRegs& r) {
-  const int t = threadIdx.x;
-  const int c0 = (t & 7) * 2;
-  const int a0 = fst_addr(c0 >> 1, t >> 3, (c0 & 1) * 16);
-  *reinterpret_cast<uint4*>(kd->sub + a0) = r.k0;
-  *reinterpret_cast<uint4*>(kd->sub + a0 + 16) = r.k1;
-  *reinterpret_cast<uint4*>(vd->sub + a0) = r.v0;
-  *reinterpret_cast<uint4*>(vd->sub + a0 + 16) = r.v1;
-}
-
-// K A-fragment: row = key (s*32 + l31), k-dim = d slice tt: contiguous b128
-__device__ inline bf16x8_vec k_afrag(const unsigned char* img, int tt, int s,
-                                     int half, int l31) {
-  return *reinterpret_cast<const bf16x8_vec*>(
-      img + fst_addr(tt, s * 32 + l31, half * 16));
-}
-
-__device__ inline int c_row(int reg, int half) {
-  return (reg & 3) + 8 * (reg >> 2) + 4 * half;
-}
-
-// tr_b16 per-lane invariant for V B-fragments (rows = keys in [64][16]
-// subtiles): sub parity (l>>4)&1, key offset (l>>5)*8 rows, chunk (l&15)*8
-__device__ inline unsigned fwd_tr_lane_off(int lane) {
-  return ((lane >> 4) & 1) * FSUBT + ((lane >> 5) * 8) * 32 + (lane & 15) * 8;
-}
-
-#define FTR_READ(dst, addr) \
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(addr))
-#define FTR_WAIT2(r0, r1) \
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r0), "+v"(r1))
-
-// sequence-row offset of head (b,h): bshd=1 = [B,S,H,D] storage (see
-// flash_attn_bwd.hip row_off)
-__device__ inline int64_t frow_off(int b, int h, int s, int H, int S, int bshd) {
-  return bshd ? (((int64_t)b * S + s) * H + h) * FWD_D
-              : (((int64_t)b * H + h) * S + s) * FWD_D;
-}
-
-__device__ inline bf16x8_vec tr_join8(unsigned long long lo,
-                                      unsigned long long hi) {
-  union {
-    struct {
-      unsigned long long lo, hi;
-    } u;
-    bf16x8_vec v;
-  } c;
-  c.u.lo = lo;
-  c.u.hi = hi;
-  return c.v;
+// K A-fragment of 32-key block s of the staged tile: row = key s*32 + l31,
+// k-dim = d slice tt. The row is formed here and not at the call site, where
+// s*32 is shared with the causal test and the register assignment shifts
+// (docs/KERNELS.md, attention tile geometry).
+__device__ inline bf16x8_vec k_afrag(const unsigned char* img, int tt, int s, int half,
+                                     int l31) {
+  return rm_frag<64>(img, tt, s * 32 + l31, half);
 }
 
 // pack two f32 into one dword of 2 bf16 (no builtin on gfx950 — T12).
@@ -171,7 +90,7 @@ __device__ inline float half_combine_sum(float v) {
   return __uint_as_float(a) + __uint_as_float(b);
 }
 
-__global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
+__global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, bf16* __restrict__ out,
     float* __restrict__ lse, int B, int Hq, int Hkv, int S, float scale,
@@ -186,8 +105,8 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
   const int half = lane >> 5;
   const int l31 = lane & 31;
 
-  const int Q0 = blockIdx.x * (FWD_WAVES * FWD_QBLK);
-  const int my_q0 = Q0 + wave * FWD_QBLK;       // this wave's 32 q rows
+  const int Q0 = blockIdx.x * (kFaWaves * kFaBlk);
+  const int my_q0 = Q0 + wave * kFaBlk;       // this wave's 32 q rows
   const int q_glob = my_q0 + l31;               // this lane's q row
   const bool active = my_q0 < S;
 
@@ -195,7 +114,7 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
   const int64_t lse_head = ((int64_t)b * Hq + hq) * S;  // lse is dense BHS
   bf16x8_vec qfrag[8];
   if (active) {
-    const int64_t q_off = frow_off(b, hq, q_glob, Hq, S, bshd);
+    const int64_t q_off = row_off(b, hq, q_glob, Hq, S, bshd);
 #pragma unroll
     for (int tt = 0; tt < 8; tt++) {
       qfrag[tt] =
@@ -203,18 +122,18 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
     }
   }
 
-  const bf16* k_base = k + frow_off(b, hkv, 0, Hkv, S, bshd);
-  const bf16* v_base = v + frow_off(b, hkv, 0, Hkv, S, bshd);
-  const int64_t kv_ld = bshd ? (int64_t)Hkv * FWD_D : FWD_D;
+  const bf16* k_base = k + row_off(b, hkv, 0, Hkv, S, bshd);
+  const bf16* v_base = v + row_off(b, hkv, 0, Hkv, S, bshd);
+  const int64_t kv_ld = bshd ? (int64_t)Hkv * kFaD : kFaD;
 
   // number of KV tiles this WORKGROUP must stage
-  const int kv_hi = causal ? min(S, Q0 + FWD_WAVES * FWD_QBLK) : S;
-  const int nT = (kv_hi + FWD_KVBLK - 1) / FWD_KVBLK;
+  const int kv_hi = causal ? min(S, Q0 + kFaWaves * kFaBlk) : S;
+  const int nT = (kv_hi + kFwdKvBlk - 1) / kFwdKvBlk;
 
   f32x16 o_acc[4] = {};
   // softmax runs in the log2 domain: m2 = max of (scale*log2e)*s, powers
   // of two via the native v_exp, one fma per element (exp2+fma fold)
-  const float c2 = scale * LOG2E;
+  const float c2 = scale * kLog2e;
   float m_run = -1e30f;
   float l_run = 0.f;
 
@@ -225,32 +144,32 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
     __builtin_amdgcn_s_setprio(1);
   }
 
-  const unsigned tr_off = fwd_tr_lane_off(lane);
+  const unsigned tr_off = Tile<64>::tr_lane_off(lane);
   float* bc = sm.bcast[wave];
 
-  KvRegs staged = load_kv(k_base, v_base, kv_ld);  // tile 0
+  TileRegs<64> staged = load_tiles<64>(k_base, v_base, kv_ld);  // tile 0
   for (int j = 0; j < nT; j++) {
     const int cur = j & 1;
-    write_kv(&sm.k_img[cur], &sm.v_img[cur], staged);
+    write_tiles(&sm.k_img[cur], &sm.v_img[cur], staged);
     __syncthreads();
     if (j + 1 < nT) {
       // issue the next tile's global loads now — they retire under this
       // tile's MFMA phase and are waited for by the write after the
       // next barrier (compiler-counted vmcnt)
-      staged = load_kv(k_base + (int64_t)(j + 1) * FWD_KVBLK * kv_ld,
-                       v_base + (int64_t)(j + 1) * FWD_KVBLK * kv_ld, kv_ld);
+      staged = load_tiles<64>(k_base + (int64_t)(j + 1) * kFwdKvBlk * kv_ld,
+                       v_base + (int64_t)(j + 1) * kFwdKvBlk * kv_ld, kv_ld);
     }
 
-    const int key0 = j * FWD_KVBLK;
+    const int key0 = j * kFwdKvBlk;
     // this wave needs the tile only if some of its keys are visible
-    if (active && (!causal || key0 <= my_q0 + FWD_QBLK - 1)) {
+    if (active && (!causal || key0 <= my_q0 + kFaBlk - 1)) {
       const unsigned char* kimg = sm.k_img[cur].sub;
       const unsigned v_img_base = (unsigned)(uintptr_t)sm.v_img[cur].sub + tr_off;
 
 #pragma unroll
       for (int s = 0; s < 2; s++) {  // two 32-key blocks per tile
         const int kb0 = key0 + s * 32;
-        if (causal && kb0 > my_q0 + FWD_QBLK - 1) break;
+        if (causal && kb0 > my_q0 + kFaBlk - 1) break;
 
         f32x16 s_acc = {};
 #pragma unroll
@@ -276,7 +195,7 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
 
         // defer-max: rescale O only when the max moved past THR
         float m_use = m_run;
-        if (!__all(bmax - m_run <= FWD_THR)) {
+        if (!__all(bmax - m_run <= kFwdThr)) {
           const float m_new = fmaxf(m_run, bmax);
           const float alpha = exp2f(m_run - m_new);  // 0 on first tile
           // broadcast alpha to O's row layout and rescale
@@ -336,13 +255,13 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
           const int dt = it & 3;
           const int h2 = it >> 2;
           const unsigned base =
-              v_img_base + dt * (2 * FSUBT) + (s * 32 + h2 * 16) * 32;
+              v_img_base + Tile<64>::tr_step_off(dt, h2) + (s * 32) * 32;
           unsigned long long t0, t1;
-          FTR_READ(t0, base);
-          FTR_READ(t1, base + 128);
-          FTR_WAIT2(t0, t1);
+          TR_READ(t0, base);
+          TR_READ(t1, base + 128);
+          TR_WAIT2_KEEP(0, t0, t1);
           o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              h2 ? pa1.v : pa0.v, tr_join8(t0, t1), o_acc[dt], 0, 0, 0);
+              h2 ? pa1.v : pa0.v, tr_join(t0, t1), o_acc[dt], 0, 0, 0);
         }
       }
     }
@@ -362,7 +281,7 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
 #pragma unroll
     for (int r = 0; r < 16; r++) {
       const int row = c_row(r, half);
-      out[frow_off(b, hq, my_q0 + row, Hq, S, bshd) + dt * 32 + l31] =
+      out[row_off(b, hq, my_q0 + row, Hq, S, bshd) + dt * 32 + l31] =
           __float2bfloat16(o_acc[dt][r] * bc[row]);
     }
   }
@@ -376,9 +295,9 @@ __global__ __launch_bounds__(FWD_THREADS, 1) void fa_fwd_kernel(
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
                    float* lse, int B, int Hq, int Hkv, int S, float scale,
                    bool causal, bool bshd, hipStream_t stream) {
-  const int rows_per_wg = FWD_WAVES * FWD_QBLK;
+  const int rows_per_wg = kFaWaves * kFaBlk;
   const int nblk = (S + rows_per_wg - 1) / rows_per_wg;
-  hipLaunchKernelGGL(fa_fwd_kernel, dim3(nblk, B * Hq), dim3(FWD_THREADS), 0,
+  hipLaunchKernelGGL(fa_fwd_kernel, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
                      stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (bf16*)out, lse, B, Hq, Hkv, S, scale, causal ? 1 : 0,
                      bshd ? 1 : 0);

@@ -114,10 +114,16 @@ void launch_outer_sgd(int dtype_code, bool has_momentum, MultiTensorTable tb,
                       float lr, float mu, bool nesterov, float alpha,
                       tft_stream stream);
 
-// flash_attn_bwd.hip --------------------------------------------------------
+// flash_attn_fwd.hip --------------------------------------------------------
+// q / k / v / out: bf16, logical [B,H,S,128]; bshd = the storage is
+// [B,S,H,128] (fa_layout.h, row_off). lse: dense fp32 [B,Hq,S]. S % 256 == 0.
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
                    float* lse, int B, int Hq, int Hkv, int S, float scale,
                    bool causal, bool bshd, tft_stream stream);
+
+// flash_attn_bwd.hip --------------------------------------------------------
+// tensors and layouts as in the forward; delta: dense fp32 [B,Hq,S], the row
+// sums of dout * o. launch_fa_bwd needs S % 128 == 0.
 void launch_fa_delta(const void* dout, const void* o, float* delta,
                      int64_t rows, int Hq, int S, bool bshd, tft_stream stream);
 void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout,

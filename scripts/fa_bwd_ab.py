@@ -1,10 +1,14 @@
 """A/B builds of the flash-attention backward kernels in one process.
 
-Each build is a stand-alone shared library of csrc/kernels/flash_attn_bwd.hip
-(the file needs nothing but the HIP headers), e.g. for the parent commit:
+Each build is a stand-alone shared library of csrc/kernels/flash_attn_bwd.hip.
+The file includes fa_tile.h / fa_layout.h / kernels.h from its own directory,
+so a copy compiled elsewhere needs -I csrc/kernels (a revision from before the
+shared headers needs nothing but the HIP headers; the -I does no harm), e.g.
+for the parent commit:
 
     git show HEAD~1:csrc/kernels/flash_attn_bwd.hip > /tmp/parent.hip
-    hipcc -O3 --offload-arch=gfx950 -shared -fPIC /tmp/parent.hip -o parent.so
+    hipcc -O3 --offload-arch=gfx950 -shared -fPIC -I csrc/kernels \
+        /tmp/parent.hip -o parent.so
     hipcc -O3 --offload-arch=gfx950 -shared -fPIC \
         csrc/kernels/flash_attn_bwd.hip -o new.so
 

@@ -1,5 +1,8 @@
-"""Custom flash-attention backward: numerics vs stock SDPA autograd + the
-MFMA layout probe (GPU)."""
+"""Custom flash-attention forward and backward: numerics vs stock SDPA / aten
+flash, both tensor layouts, what the bindings refuse, and the MFMA layout
+probe (GPU)."""
+
+import functools
 
 import pytest
 import torch
@@ -90,6 +93,27 @@ class TestCustomForward:
         torch.testing.assert_close(out, ref, rtol=2e-2, atol=2e-2)
         torch.testing.assert_close(lse, ref_lse.float(), rtol=1e-3, atol=1e-3)
 
+    @pytest.mark.parametrize("causal", [True, False])
+    @pytest.mark.parametrize("B,Hq,Hkv,S", [(1, 2, 1, 256), (1, 4, 2, 768)])
+    def test_smallest_shapes_both_layouts(self, causal, B, Hq, Hkv, S):
+        """S=256: one workgroup, four key tiles when full, the causal diagonal
+        inside every wave. S=768: three workgroups, the first causal one stages
+        4 of the 12 key tiles. Packed and through [B,S,H,D] views."""
+        from torchft_amd.ops import hip_ext
+
+        q, k, v, ref, ref_lse = _small_fwd_case(B, Hq, Hkv, S, causal)
+        scale = 128 ** -0.5
+        out_v, lse_v = hip_ext().fa_fwd(q, k, v, scale, causal)  # BSHD views
+        out_c, lse_c = hip_ext().fa_fwd(
+            q.contiguous(), k.contiguous(), v.contiguous(), scale, causal
+        )
+        for out, lse in ((out_c, lse_c), (out_v, lse_v)):
+            torch.testing.assert_close(out, ref, rtol=2e-2, atol=2e-2)
+            torch.testing.assert_close(lse, ref_lse, rtol=1e-3, atol=1e-3)
+        assert not out_v.is_contiguous() and out_c.is_contiguous()
+        assert torch.equal(out_v, out_c)
+        assert torch.equal(lse_v, lse_c)
+
     def test_full_custom_fwd_bwd(self, monkeypatch):
         """Custom fwd feeding the custom bwd must match stock end to end."""
         from torchft_amd.ops.flash_attention import _FlashAttentionFn
@@ -119,6 +143,97 @@ class TestCustomForward:
         torch.testing.assert_close(q.grad, q2.grad, rtol=5e-2, atol=5e-2)
         torch.testing.assert_close(k.grad, k2.grad, rtol=5e-2, atol=5e-2)
         torch.testing.assert_close(v.grad, v2.grad, rtol=5e-2, atol=5e-2)
+
+
+@functools.lru_cache(maxsize=None)
+def _small_fwd_case(B, Hq, Hkv, S, causal):
+    """Inputs as [B,S,H,D]-backed transpose views and aten flash's out / lse
+    for them, computed once per case."""
+    g = torch.Generator(device="cuda").manual_seed(24)
+
+    def mk(H):
+        return torch.randn(B, S, H, 128, device="cuda", dtype=torch.bfloat16,
+                           generator=g).transpose(1, 2)
+
+    q, k, v = mk(Hq), mk(Hkv), mk(Hkv)
+    ref, ref_lse, *_ = torch.ops.aten._scaled_dot_product_flash_attention(
+        q, k, v, 0.0, causal, False, scale=128 ** -0.5
+    )
+    return q, k, v, ref, ref_lse.float()
+
+
+class TestRefusals:
+    """The bindings hold every tensor to one rule and refuse before anything
+    is launched. Every bad argument is LARGER than the good one."""
+
+    B, Hq, Hkv, S = 1, 2, 1, 256
+
+    def _good(self):
+        def mk(*shape, dtype=torch.bfloat16):
+            return torch.zeros(*shape, device="cuda", dtype=dtype)
+
+        return dict(
+            q=mk(self.B, self.Hq, self.S, 128), k=mk(self.B, self.Hkv, self.S, 128),
+            v=mk(self.B, self.Hkv, self.S, 128), dout=mk(self.B, self.Hq, self.S, 128),
+            out=mk(self.B, self.Hq, self.S, 128),
+            lse=mk(self.B, self.Hq, self.S, dtype=torch.float32),
+            delta=mk(self.B, self.Hq, self.S, dtype=torch.float32),
+        )
+
+    def _fwd(self, a):
+        from torchft_amd.ops import hip_ext
+        return hip_ext().fa_fwd(a["q"], a["k"], a["v"], 128 ** -0.5, True)
+
+    def _bwd(self, a):
+        from torchft_amd.ops import hip_ext
+        return hip_ext().fa_bwd(a["q"], a["k"], a["v"], a["dout"], a["lse"],
+                                a["delta"], 128 ** -0.5, True)
+
+    def _delta(self, a):
+        from torchft_amd.ops import hip_ext
+        return hip_ext().fa_delta(a["dout"], a["out"])
+
+    def test_good_arguments_pass(self):
+        a = self._good()
+        self._fwd(a)
+        self._bwd(a)
+        self._delta(a)
+        torch.cuda.synchronize()
+
+    @pytest.mark.parametrize("call", ["_fwd", "_bwd"])
+    def test_k_twice_the_sequence(self, call):
+        a = self._good()
+        a["k"] = torch.zeros(self.B, self.Hkv, 2 * self.S, 128, device="cuda",
+                             dtype=torch.bfloat16)
+        with pytest.raises(RuntimeError, match=r"fa_(fwd|bwd): k must have q's batch and "):
+            getattr(self, call)(a)
+
+    @pytest.mark.parametrize("call", ["_fwd", "_bwd"])
+    def test_v_fp16(self, call):
+        a = self._good()
+        a["v"] = a["v"].half()
+        with pytest.raises(RuntimeError, match=r"fa_(fwd|bwd): v must be a 4-D bf16"):
+            getattr(self, call)(a)
+
+    def test_dout_twice_the_heads(self):
+        a = self._good()
+        a["dout"] = torch.zeros(self.B, 2 * self.Hq, self.S, 128, device="cuda",
+                                dtype=torch.bfloat16)
+        with pytest.raises(RuntimeError, match=r"fa_bwd: dout must have the shape"):
+            self._bwd(a)
+
+    def test_delta_twice_the_elements(self):
+        a = self._good()
+        a["delta"] = torch.zeros(self.B, self.Hq, 2 * self.S, device="cuda")
+        with pytest.raises(RuntimeError, match=r"fa_bwd: delta shape mismatch"):
+            self._bwd(a)
+
+    def test_delta_out_twice_the_sequence(self):
+        a = self._good()
+        a["out"] = torch.zeros(self.B, self.Hq, 2 * self.S, 128, device="cuda",
+                               dtype=torch.bfloat16)
+        with pytest.raises(RuntimeError, match=r"fa_delta: out must have the shape"):
+            self._delta(a)
 
 
 class TestFaDelta:
