@@ -585,6 +585,26 @@ struct FaArgs {
     return t.contiguous().to(at::kFloat);
   }
 
+  // doc_start / doc_end, the document mask: both or neither, only with
+  // causal, each int32 on q's device with B*S elements, made contiguous
+  void add_doc(const c10::optional<at::Tensor>& ds, const c10::optional<at::Tensor>& de,
+               bool causal) {
+    TORCH_CHECK(ds.has_value() == de.has_value(), what, ": ",
+                ds.has_value() ? "doc_end" : "doc_start", " is missing (doc_start and ",
+                "doc_end are given together or not at all)");
+    if (!ds.has_value()) return;
+    TORCH_CHECK(causal, what, ": doc_start / doc_end need causal=True");
+    doc_start = doc("doc_start", *ds);
+    doc_end = doc("doc_end", *de);
+  }
+  // null without a mask
+  const int* doc_start_ptr() const {
+    return doc_start.defined() ? doc_start.data_ptr<int>() : nullptr;
+  }
+  const int* doc_end_ptr() const {
+    return doc_end.defined() ? doc_end.data_ptr<int>() : nullptr;
+  }
+
   const at::Tensor& q() const { return ts[0]; }
   // tensor i as the kernels read it
   at::Tensor in(size_t i) const { return bshd ? ts[i] : ts[i].contiguous(); }
@@ -600,6 +620,16 @@ struct FaArgs {
   }
 
  private:
+  at::Tensor doc_start, doc_end;
+
+  at::Tensor doc(const char* name, const at::Tensor& t) const {
+    TORCH_CHECK(t.scalar_type() == at::kInt, what, ": ", name,
+                " must be an int32 tensor, got ", t.scalar_type());
+    TORCH_CHECK(t.device() == q().device(), what, ": ", name, " must be on q's device");
+    TORCH_CHECK(t.numel() == q().size(0) * q().size(2), what, ": ", name,
+                " shape mismatch (", t.numel(), " elements, need B*S)");
+    return t.contiguous();
+  }
   void check_kind(const char* name, const at::Tensor& t) const {
     TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 4, what, ": ", name,
                 " must be a 4-D bf16 tensor, got ", t.dim(), "-D ", t.scalar_type());
@@ -630,24 +660,31 @@ at::Tensor fa_delta(at::Tensor dout, at::Tensor out) {
 }
 
 std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
-                               double scale, bool causal) {
+                               double scale, bool causal,
+                               c10::optional<at::Tensor> doc_start,
+                               c10::optional<at::Tensor> doc_end) {
   FaArgs a("fa_fwd", "q", q, /*seq_multiple=*/256);
   a.add_kv(k, v);
+  a.add_doc(doc_start, doc_end, causal);
   auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
   auto out = a.out_like(0);
   auto lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
   tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
                      lse.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)k.size(1),
-                     (int)q.size(2), (float)scale, causal, a.bshd, current_stream());
+                     (int)q.size(2), (float)scale, causal, a.bshd, a.doc_start_ptr(),
+                     a.doc_end_ptr(), current_stream());
   return {out, lse};
 }
 
 std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                at::Tensor dout, at::Tensor lse, at::Tensor delta,
-                               double scale, bool causal) {
+                               double scale, bool causal,
+                               c10::optional<at::Tensor> doc_start,
+                               c10::optional<at::Tensor> doc_end) {
   FaArgs a("fa_bwd", "q", q, /*seq_multiple=*/128);
   a.add_kv(k, v);
   a.add("dout", dout);
+  a.add_doc(doc_start, doc_end, causal);
   auto lsec = a.stat("lse", lse), deltac = a.stat("delta", delta);
   auto qc = a.in(0), kc = a.in(1), vc = a.in(2), doc = a.in(3);
   auto dq = a.out_like(0), dk = a.out_like(1), dv = a.out_like(2);
@@ -655,7 +692,7 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                      lsec.data_ptr<float>(), deltac.data_ptr<float>(), dq.data_ptr(),
                      dk.data_ptr(), dv.data_ptr(), (int)q.size(0), (int)q.size(1),
                      (int)k.size(1), (int)q.size(2), (float)scale, causal, a.bshd,
-                     current_stream());
+                     a.doc_start_ptr(), a.doc_end_ptr(), current_stream());
   return {dq, dk, dv};
 }
 
@@ -729,9 +766,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "multi-tensor outs[i] = minuends[i] - subtrahends[i]");
   m.def("diloco_outer_step", &diloco_outer_step,
         "fused DiLoCo outer SGD step, re-snapshot and local-progress lerp");
-  m.def("fa_fwd", &fa_fwd);
+  m.def("fa_fwd", &fa_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("causal"), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none(),
+        "flash-attention forward (bf16, D=128): returns (out, lse)");
   m.def("fa_delta", &fa_delta);
-  m.def("fa_bwd", &fa_bwd,
+  m.def("fa_bwd", &fa_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
+        py::arg("lse"), py::arg("delta"), py::arg("scale"), py::arg("causal"),
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none(),
         "flash-attention backward (bf16, D=128): returns (dq, dk, dv)");
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd,
         "fused cross-entropy: returns row_loss, writes the gradient in place");

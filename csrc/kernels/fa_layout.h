@@ -1,8 +1,9 @@
 // Address math of the flash-attention kernels (flash_attn_fwd.hip,
 // flash_attn_bwd.hip): the sizes, the subtiled LDS tile image, the
-// thread -> chunk staging map, the tr_b16 read offsets and the pa/pb swizzle.
-// Plain constexpr C++, callable from host and device; the device-only pieces
-// built on it are in fa_tile.h. csrc/kernels/tests/fa_layout_test.cpp checks
+// thread -> chunk staging map, the tr_b16 read offsets, the pa/pb swizzle and
+// the tile bounds of the document mask. Plain constexpr C++, callable from
+// host and device; the device-only pieces built on it are in fa_tile.h.
+// csrc/kernels/tests/fa_layout_test.cpp and fa_doc_bounds_test.cpp check
 // every function here on the host.
 #pragma once
 
@@ -84,6 +85,50 @@ TFT_HD constexpr int64_t row_off(int b, int h, int s, int H, int S, int bshd) {
 // row of C/D register `reg` of a 32x32 MFMA in lane half `half` (col = l31)
 TFT_HD constexpr int c_row(int reg, int half) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * half;
+}
+
+// ---- document mask (causal within a document) -------------------------------
+// Key j is visible to query i iff doc_start[i] <= j <= i, equally
+// j <= i < doc_end[j]; both arrays are non-decreasing when DocMask built them.
+// The kernels read them as they are: every bound below is clamped into the
+// range the causal kernel uses, whatever int32 the arrays hold, so garbage
+// costs correctness of the values and never an address
+// (csrc/kernels/tests/fa_doc_bounds_test.cpp).
+TFT_HD constexpr int fa_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Forward and dq: the first 64-key tile a workgroup streams. ds_first is
+// doc_start of the workgroup's first query row (the smallest of its rows), nT
+// the causal tile count (>= 1).
+TFT_HD constexpr int doc_first_tile(int ds_first, int nT) {
+  return fa_clamp(ds_first / 64, 0, nT - 1);
+}
+// Forward and dq, per wave: the 32-key block at kb0 ends before doc_start of
+// the wave's first row, so none of its keys is visible to any of the 32 rows.
+TFT_HD constexpr bool doc_block_skipped(int kb0, int ds_wave_first) {
+  return kb0 + 31 < ds_wave_first;
+}
+// ... and the block needs the per-element test only if its first key lies
+// below doc_start of the wave's last row.
+TFT_HD constexpr bool doc_block_straddles(int kb0, int ds_wave_last) {
+  return kb0 < ds_wave_last;
+}
+// the per-element test itself, on top of the causal one
+TFT_HD constexpr bool doc_visible(int key, int ds_q) { return key >= ds_q; }
+
+// dkdv: one past the last 32-query tile a workgroup streams. de_last is
+// doc_end of the workgroup's last key (the largest of its keys); the causal
+// range is [i_min, nQ) with i_min < nQ, and at least one tile stays.
+TFT_HD constexpr int doc_last_qtile(int de_last, int i_min, int nQ) {
+  return fa_clamp((fa_clamp(de_last, 0, nQ * kFaBlk) + kFaBlk - 1) / kFaBlk, i_min + 1, nQ);
+}
+// dkdv, per wave: query tile i starts at or past doc_end of the wave's last key
+TFT_HD constexpr bool doc_qtile_skipped(int i, int de_wave_last) {
+  return i * kFaBlk >= de_wave_last;
+}
+// ... and the tile needs the per-element test only if doc_start of its last
+// query lies above the first key of the wave's block jb
+TFT_HD constexpr bool doc_qtile_straddles(int ds_tile_last, int jb) {
+  return ds_tile_last > jb * kFaBlk;
 }
 
 // pa/pb: a wave's 32 x 64 B transpose buffer (P or dS as bf16, [row][32 keys]),

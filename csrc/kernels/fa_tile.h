@@ -64,6 +64,19 @@ __device__ inline bf16x8_vec pb_afrag(const unsigned char* pb, int h2, int half,
   return *reinterpret_cast<const bf16x8_vec*>(pb + pb_afrag_addr(h2, half, l31));
 }
 
+// The DOC (document mask) kernel variants take their int32 arrays as a
+// trailing parameter pack, so that the plain instantiations keep the parameter
+// list, the kernarg layout and with them the code they had without the mask.
+// doc_ptr<I>(pack...) is array I of the pack.
+template <int I, class... R>
+__device__ inline const int* doc_ptr(const int* first, R... rest) {
+  if constexpr (I == 0) {
+    return first;
+  } else {
+    return doc_ptr<I - 1>(rest...);
+  }
+}
+
 // one hardware-transpose read: 4 bf16 = column (l&15), rows j=0..3 of the
 // [4][16] block at (per-lane) byte address `addr` into the LDS image
 #define TR_READ(dst, addr) \

@@ -32,11 +32,19 @@
 // dV/dK phase double-buffer its tr_b16 reads. The arithmetic is untouched:
 // results are bit-identical to the v3 loop.
 //
+// Document mask (DOC variants): causal within the documents of a packed row.
+// dkdv ends its query-tile stream where the documents of its keys end, dq
+// starts its key-tile stream where the documents of its rows start, and the
+// per-element test runs only in tiles that straddle a boundary (bounds:
+// fa_layout.h; docs/KERNELS.md).
+//
 // MFMA lane mappings (verified by mfma_probe.hip on gfx950):
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "fa_tile.h"
 
@@ -60,12 +68,17 @@ struct SmemFA {
 };
 
 // ---- kernel 1: dK/dV ------------------------------------------------------
+// DOC (both kernels): the document-mask variant (docs/KERNELS.md, "document
+// mask"). Its arrays ride in the trailing pack (fa_tile.h, doc_ptr): dkdv
+// takes doc_start and doc_end, dq doc_start alone.
+template <bool DOC, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     bf16* __restrict__ dk, bf16* __restrict__ dv, int B, int Hq, int Hkv,
-    int S, float scale, int causal, int bshd) {
+    int S, float scale, int causal, int bshd, DocP... docp) {
+  static_assert(sizeof...(DocP) == (DOC ? 2 : 0), "DOC takes doc_start, doc_end");
   __shared__ SmemFA sm;
   const int G = Hq / Hkv;
   const int b = blockIdx.y / Hkv;
@@ -78,7 +91,20 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
   const bool active = jb * kFaBlk < S;
   const int nQ = S / kFaBlk;
   const int i_min = causal ? blockIdx.x * kFaWaves : 0;
-  const int nI = nQ - i_min;
+  // DOC: the query tiles end where the document of the workgroup's last key
+  // ends; a wave stops computing at doc_end of its own last key (de_w)
+  int i_hi = nQ, de_w = 0;
+  const int* ds_base = nullptr;
+  if constexpr (DOC) {
+    ds_base = doc_ptr<0>(docp...) + (int64_t)b * S;
+    const int* doc_end = doc_ptr<1>(docp...) + (int64_t)b * S;
+    const int wg_last = min((int)(blockIdx.x + 1) * kFaWaves * kFaBlk, S) - 1;
+    i_hi = doc_last_qtile(doc_end[wg_last], i_min, nQ);
+    if (active) {
+      de_w = __builtin_amdgcn_readfirstlane(doc_end[jb * kFaBlk + kFaBlk - 1]);
+    }
+  }
+  const int nI = (DOC ? i_hi : nQ) - i_min;
   const int T = G * nI;  // flattened (g, i) iteration count
 
   // K fragments in VGPRs (the wave's fixed A-operand); V in wave-private
@@ -120,6 +146,9 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
   TileRegs<32> nxt = load_tiles<32>(tile_src(0, q), tile_src(0, dout), q_ld);
   float lse_n = lse_base[i_min * kFaBlk + l31];
   float delta_n = delta_base[i_min * kFaBlk + l31];
+  // DOC: doc_start of the lane's query, staged beside lse / delta
+  int ds_n = 0;
+  if constexpr (DOC) ds_n = ds_base[i_min * kFaBlk + l31];
   write_tiles(&sm.img[0].a, &sm.img[0].b, nxt);
   __syncthreads();
 
@@ -129,8 +158,10 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
 
     const float lse_q = lse_n;
     const float delta_q = delta_n;
+    const int ds_q = ds_n;
     const bool more = t + 1 < T;  // wave-uniform
-    const bool computes = active && !(causal && i < jb);
+    const bool computes =
+        active && !(causal && i < jb) && !(DOC && doc_qtile_skipped(i, de_w));
 
     // phase 1: S^T, dP^T, then P / dS into the wave's pa / pb
     if (computes) {
@@ -158,6 +189,21 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
       // q row minus the lane's first key row: the causal test of C register
       // rg is one compare against the constant c_row(rg, 0)
       const int qk = (i - jb) * kFaBlk + l31 - 4 * half;
+      // DOC: only a tile that straddles a boundary (wave-uniform test) has
+      // keys below doc_start of its queries. Their scores become -inf there,
+      // so the loop below, unchanged, gives them P = exp(-inf) = 0 and dS = 0.
+      // dsk = doc_start of the lane's query minus the lane's first key row,
+      // the causal test's form: key >= doc_start is c_row(rg, 0) >= dsk. The
+      // clamp keeps the difference in range for any int32.
+      if constexpr (DOC) {
+        if (doc_qtile_straddles(__builtin_amdgcn_readlane(ds_q, 31), jb)) {
+          const int dsk = fa_clamp(ds_q, 0, S) - jb * kFaBlk - 4 * half;
+#pragma unroll
+          for (int rg = 0; rg < 16; rg++) {
+            if (c_row(rg, 0) < dsk) s_acc[rg] = -INFINITY;
+          }
+        }
+      }
 #pragma unroll
       for (int rg = 0; rg < 16; rg++) {
         const bool valid = !causal || (qk >= c_row(rg, 0));
@@ -180,6 +226,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
       nxt = load_tiles<32>(tile_src(t + 1, q), tile_src(t + 1, dout), q_ld);
       lse_n = lse_base[st];
       delta_n = delta_base[st];
+      if constexpr (DOC) ds_n = ds_base[(i_min + (t + 1) % nI) * kFaBlk + l31];
     }
 
     if (computes) {
@@ -261,15 +308,22 @@ struct SmemDq {
   Tile<64> v_img[2];
   alignas(16) unsigned char pb[kFaWaves][32 * 64];
 };
+// DOC: each wave keeps doc_start of its 32 query rows in LDS. The rows are C
+// registers in dq, and sixteen more live VGPRs do not fit.
+struct SmemDqDoc : SmemDq {
+  alignas(16) int ds_row[kFaWaves][32];
+};
 
 // ---- kernel 2: dQ ---------------------------------------------------------
+template <bool DOC, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     bf16* __restrict__ dq, int B, int Hq, int Hkv, int S, float scale,
-    int causal, int bshd) {
-  __shared__ SmemDq sm;
+    int causal, int bshd, DocP... docp) {
+  static_assert(sizeof...(DocP) == (DOC ? 1 : 0), "DOC takes doc_start");
+  __shared__ std::conditional_t<DOC, SmemDqDoc, SmemDq> sm;
   const int G = Hq / Hkv;
   const int b = blockIdx.y / Hq;
   const int hq = blockIdx.y % Hq;
@@ -307,6 +361,21 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
 
   f32x16 dq_acc[4] = {};
 
+  // DOC: as in the forward, the workgroup streams from the tile that holds
+  // doc_start of its first row, a wave skips the blocks below doc_start of
+  // its first row (ds_w0) and tests per element only below that of its last
+  // row (ds_w1).
+  int j0 = 0, ds_w0 = 0, ds_w1 = 0;
+  if constexpr (DOC) {
+    const int* doc_start = doc_ptr<0>(docp...) + (int64_t)b * S;
+    j0 = doc_first_tile(doc_start[bx * kFaWaves * kFaBlk], T);
+    int ds_lane = 0;
+    if (active) ds_lane = doc_start[ib * kFaBlk + l31];
+    if (half == 0) sm.ds_row[wave][l31] = ds_lane;
+    ds_w0 = __builtin_amdgcn_readlane(ds_lane, 0);
+    ds_w1 = __builtin_amdgcn_readlane(ds_lane, 31);
+  }
+
   const int64_t kv_ld = bshd ? (int64_t)Hkv * kFaD : kFaD;
   const unsigned tr_off = Tile<64>::tr_lane_off(lane);
 
@@ -315,19 +384,20 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     return load_tiles<64>(k + off, v + off, kv_ld);
   };
 
-  // prologue: stage key tile 0
-  TileRegs<64> pre = tile_regs(0);
-  write_tiles(&sm.k_img[0], &sm.v_img[0], pre);
+  // prologue: stage key tile 0 (DOC: the first tile needed)
+  TileRegs<64> pre = tile_regs(DOC ? j0 : 0);
+  write_tiles(&sm.k_img[DOC ? j0 & 1 : 0], &sm.v_img[DOC ? j0 & 1 : 0], pre);
   __syncthreads();
 
-  for (int j = 0; j < T; j++) {
+  for (int j = DOC ? j0 : 0; j < T; j++) {
     const int cur = j & 1;
     // T14 split: key tile j+1's global loads land under tile j's MFMAs.
     // Wave-uniform guard: the last tile forms no address.
     const bool more = j + 1 < T;
     if (more) pre = tile_regs(j + 1);
 
-    if (active && !(causal && j * 64 > ib * kFaBlk + kFaBlk - 1)) {
+    if (active && !(causal && j * 64 > ib * kFaBlk + kFaBlk - 1) &&
+        !(DOC && doc_block_skipped(j * 64 + 32, ds_w0))) {
       const unsigned char* kimg = sm.k_img[cur].sub;
       const unsigned char* vimg = sm.v_img[cur].sub;
       const unsigned a_base = (unsigned)(uintptr_t)kimg + tr_off;
@@ -337,6 +407,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
       for (int s = 0; s < 2; s++) {  // two 32-key halves per staged tile
         const int kb0 = j * 64 + s * 32;
         if (causal && kb0 > ib * kFaBlk + kFaBlk - 1) break;
+        if (DOC && doc_block_skipped(kb0, ds_w0)) continue;
 
         f32x16 s_acc = {};
         f32x16 dp_acc = {};
@@ -352,6 +423,24 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
         // key minus the lane's first q row: the causal test of C register
         // rg is one compare against the constant c_row(rg, 0)
         const int kq = kg - ib * kFaBlk - 4 * half;
+        // DOC: only a block that straddles a boundary (wave-uniform test) has
+        // keys below doc_start of some row. Their scores become -inf there, so
+        // the loop below, unchanged, gives them P = exp(-inf) = 0 and dS = 0.
+        // The rows' doc_start come from the wave's LDS copy, four consecutive
+        // rows per 16-B read.
+        if constexpr (DOC) {
+          if (doc_block_straddles(kb0, ds_w1)) {
+#pragma unroll
+            for (int r4 = 0; r4 < 4; r4++) {
+              const int4 d4 =
+                  *reinterpret_cast<const int4*>(&sm.ds_row[wave][c_row(4 * r4, half)]);
+              if (!doc_visible(kg, d4.x)) s_acc[4 * r4] = -INFINITY;
+              if (!doc_visible(kg, d4.y)) s_acc[4 * r4 + 1] = -INFINITY;
+              if (!doc_visible(kg, d4.z)) s_acc[4 * r4 + 2] = -INFINITY;
+              if (!doc_visible(kg, d4.w)) s_acc[4 * r4 + 3] = -INFINITY;
+            }
+          }
+        }
 #pragma unroll
         for (int rg = 0; rg < 16; rg++) {
           const bool valid = !causal || (c_row(rg, 0) >= kq);
@@ -456,13 +545,26 @@ void launch_fa_delta(const void* dout, const void* o, float* delta,
 void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout,
                    const float* lse, const float* delta, void* dq, void* dk,
                    void* dv, int B, int Hq, int Hkv, int S, float scale,
-                   bool causal, bool bshd, hipStream_t stream) {
+                   bool causal, bool bshd, const int* doc_start, const int* doc_end,
+                   hipStream_t stream) {
   const int nblk = (S + kFaBlk * kFaWaves - 1) / (kFaBlk * kFaWaves);
-  hipLaunchKernelGGL(fa_bwd_dkdv_kernel, dim3(nblk, B * Hkv), dim3(kFaThreads), 0,
+  if (doc_start != nullptr && doc_end != nullptr) {
+    hipLaunchKernelGGL((fa_bwd_dkdv_kernel<true, const int*, const int*>),
+                       dim3(nblk, B * Hkv), dim3(kFaThreads), 0, stream, (const bf16*)q,
+                       (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta,
+                       (bf16*)dk, (bf16*)dv, B, Hq, Hkv, S, scale, 1, bshd ? 1 : 0,
+                       doc_start, doc_end);
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, const int*>), dim3(nblk, B * Hq),
+                       dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq,
+                       Hkv, S, scale, 1, bshd ? 1 : 0, doc_start);
+    return;
+  }
+  hipLaunchKernelGGL(fa_bwd_dkdv_kernel<false>, dim3(nblk, B * Hkv), dim3(kFaThreads), 0,
                      stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, B, Hq,
                      Hkv, S, scale, causal ? 1 : 0, bshd ? 1 : 0);
-  hipLaunchKernelGGL(fa_bwd_dq_kernel, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
+  hipLaunchKernelGGL(fa_bwd_dq_kernel<false>, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
                      stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq, Hkv, S,
                      scale, causal ? 1 : 0, bshd ? 1 : 0);

@@ -27,6 +27,11 @@
 //   before this block's P is exponentiated, and l folds alpha in the same
 //   update (l = l*alpha + sum_p).
 //
+//   Document mask (DOC variant): causal within the documents of a packed
+//   row. Key tiles outside the workgroup's / wave's documents are not
+//   streamed or computed; the per-element test runs only in blocks that
+//   straddle a boundary (bounds: fa_layout.h; docs/KERNELS.md).
+//
 // MFMA lane mappings (mfma_probe.hip):
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
@@ -90,11 +95,16 @@ __device__ inline float half_combine_sum(float v) {
   return __uint_as_float(a) + __uint_as_float(b);
 }
 
+// DOC: the document-mask variant (docs/KERNELS.md, "document mask"). Its one
+// extra argument, doc_start (int32 [B,S]), rides in the trailing pack so that
+// the plain instantiation keeps its parameter list and its code.
+template <bool DOC, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, bf16* __restrict__ out,
     float* __restrict__ lse, int B, int Hq, int Hkv, int S, float scale,
-    int causal, int bshd) {
+    int causal, int bshd, DocP... docp) {
+  static_assert(sizeof...(DocP) == (DOC ? 1 : 0), "DOC takes doc_start");
   __shared__ SmemFwd sm;
   const int G = Hq / Hkv;
   const int b = blockIdx.y / Hq;
@@ -130,6 +140,19 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
   const int kv_hi = causal ? min(S, Q0 + kFaWaves * kFaBlk) : S;
   const int nT = (kv_hi + kFwdKvBlk - 1) / kFwdKvBlk;
 
+  // DOC: the workgroup streams from the tile that holds doc_start of its
+  // first row; a wave skips the blocks below doc_start of its own first row
+  // (ds_w0) and masks per element only below that of its last row (ds_w1).
+  // The lane's q is its MFMA column, so the element test is lane-local.
+  int j0 = 0, ds_q = 0, ds_w0 = 0, ds_w1 = 0;
+  if constexpr (DOC) {
+    const int* doc_start = doc_ptr<0>(docp...) + (int64_t)b * S;
+    j0 = doc_first_tile(doc_start[Q0], nT);
+    if (active) ds_q = doc_start[q_glob];
+    ds_w0 = __builtin_amdgcn_readlane(ds_q, 0);
+    ds_w1 = __builtin_amdgcn_readlane(ds_q, 31);
+  }
+
   f32x16 o_acc[4] = {};
   // softmax runs in the log2 domain: m2 = max of (scale*log2e)*s, powers
   // of two via the native v_exp, one fma per element (exp2+fma fold)
@@ -147,8 +170,11 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
   const unsigned tr_off = Tile<64>::tr_lane_off(lane);
   float* bc = sm.bcast[wave];
 
-  TileRegs<64> staged = load_tiles<64>(k_base, v_base, kv_ld);  // tile 0
-  for (int j = 0; j < nT; j++) {
+  TileRegs<64> staged =  // tile 0 (DOC: the first tile needed)
+      DOC ? load_tiles<64>(k_base + (int64_t)j0 * kFwdKvBlk * kv_ld,
+                           v_base + (int64_t)j0 * kFwdKvBlk * kv_ld, kv_ld)
+          : load_tiles<64>(k_base, v_base, kv_ld);
+  for (int j = DOC ? j0 : 0; j < nT; j++) {
     const int cur = j & 1;
     write_tiles(&sm.k_img[cur], &sm.v_img[cur], staged);
     __syncthreads();
@@ -162,7 +188,8 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
 
     const int key0 = j * kFwdKvBlk;
     // this wave needs the tile only if some of its keys are visible
-    if (active && (!causal || key0 <= my_q0 + kFaBlk - 1)) {
+    if (active && (!causal || key0 <= my_q0 + kFaBlk - 1) &&
+        !(DOC && doc_block_skipped(key0 + 32, ds_w0))) {
       const unsigned char* kimg = sm.k_img[cur].sub;
       const unsigned v_img_base = (unsigned)(uintptr_t)sm.v_img[cur].sub + tr_off;
 
@@ -170,6 +197,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
       for (int s = 0; s < 2; s++) {  // two 32-key blocks per tile
         const int kb0 = key0 + s * 32;
         if (causal && kb0 > my_q0 + kFaBlk - 1) break;
+        if (DOC && doc_block_skipped(kb0, ds_w0)) continue;
 
         f32x16 s_acc = {};
 #pragma unroll
@@ -191,7 +219,27 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
           p[r] = sv;
           bmax = fmaxf(bmax, sv);
         }
-        bmax = half_combine_max(bmax) * c2;  // both 16-key halves of this q
+        // DOC: the document test, only in the blocks that straddle a boundary
+        // (wave-uniform branch: the other blocks run the causal code)
+        bool dstr = false;
+        if constexpr (DOC) dstr = doc_block_straddles(kb0, ds_w1);
+        if (dstr) {
+          bmax = -1e30f;
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            if (!doc_visible(kb0 + c_row(r, half), ds_q)) p[r] = -1e30f;
+            bmax = fmaxf(bmax, p[r]);
+          }
+        }
+        bmax = half_combine_max(bmax);  // both 16-key halves of this q
+        // DOC: a row with no visible key in this block (its document starts
+        // further down the wave's rows) must not move: without the guard a
+        // row that has seen nothing yet would take m = -1e30 * c2 and give
+        // its masked keys exp2(0) = 1. Its bmax stands in as m_run (no
+        // rescale request, alpha = 1 if another row asks) and its P is 0.
+        // Causality alone leaves every row of a streamed block its key kb0.
+        const bool dead = dstr && bmax <= -1e30f;
+        bmax = dead ? m_run : bmax * c2;
 
         // defer-max: rescale O only when the max moved past THR
         float m_use = m_run;
@@ -224,6 +272,11 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
           const float e1 = exp2f(fmaf(p[2 * i + 1], c2, -m_use));
           psum += e0 + e1;
           pk[i] = cvt_pk_bf16(e0, e1);
+        }
+        if (dstr && dead) {  // whatever exp2 made of the sentinels
+          psum = 0.f;
+#pragma unroll
+          for (int i = 0; i < 8; i++) pk[i] = 0u;
         }
         l_run += half_combine_sum(psum);
 
@@ -294,10 +347,19 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
 
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
                    float* lse, int B, int Hq, int Hkv, int S, float scale,
-                   bool causal, bool bshd, hipStream_t stream) {
+                   bool causal, bool bshd, const int* doc_start, const int* doc_end,
+                   hipStream_t stream) {
   const int rows_per_wg = kFaWaves * kFaBlk;
   const int nblk = (S + rows_per_wg - 1) / rows_per_wg;
-  hipLaunchKernelGGL(fa_fwd_kernel, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
+  (void)doc_end;  // the forward is query-centric: doc_start says it all
+  if (doc_start != nullptr) {
+    hipLaunchKernelGGL((fa_fwd_kernel<true, const int*>), dim3(nblk, B * Hq),
+                       dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, lse, B, Hq, Hkv, S, scale, 1,
+                       bshd ? 1 : 0, doc_start);
+    return;
+  }
+  hipLaunchKernelGGL(fa_fwd_kernel<false>, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
                      stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (bf16*)out, lse, B, Hq, Hkv, S, scale, causal ? 1 : 0,
                      bshd ? 1 : 0);

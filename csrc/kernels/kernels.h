@@ -117,9 +117,12 @@ void launch_outer_sgd(int dtype_code, bool has_momentum, MultiTensorTable tb,
 // flash_attn_fwd.hip --------------------------------------------------------
 // q / k / v / out: bf16, logical [B,H,S,128]; bshd = the storage is
 // [B,S,H,128] (fa_layout.h, row_off). lse: dense fp32 [B,Hq,S]. S % 256 == 0.
+// doc_start / doc_end: the document mask (fa_layout.h), dense int32 [B,S]
+// device arrays, both null for no mask and given only with causal.
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
                    float* lse, int B, int Hq, int Hkv, int S, float scale,
-                   bool causal, bool bshd, tft_stream stream);
+                   bool causal, bool bshd, const int* doc_start, const int* doc_end,
+                   tft_stream stream);
 
 // flash_attn_bwd.hip --------------------------------------------------------
 // tensors and layouts as in the forward; delta: dense fp32 [B,Hq,S], the row
@@ -129,7 +132,8 @@ void launch_fa_delta(const void* dout, const void* o, float* delta,
 void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout,
                    const float* lse, const float* delta, void* dq, void* dk,
                    void* dv, int B, int Hq, int Hkv, int S, float scale,
-                   bool causal, bool bshd, tft_stream stream);
+                   bool causal, bool bshd, const int* doc_start, const int* doc_end,
+                   tft_stream stream);
 
 // fused_cross_entropy.hip ---------------------------------------------------
 // logits: bf16 [rows, V] contiguous, overwritten with the gradient when

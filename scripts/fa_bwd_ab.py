@@ -31,18 +31,25 @@ import torch
 
 from torchft_amd.ops import hip_ext
 
+# launch_fa_bwd as it is now (two document-mask arrays before the stream,
+# passed as null here) and as it was before the document mask
 _SYM = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
-        "iiiifbbP12ihipStream_t")
+        "iiiifbbPKiS6_P12ihipStream_t")
+_SYM_NO_DOC = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
+               "iiiifbbP12ihipStream_t")
 D = 128
 
 
 class Build:
     def __init__(self, spec):
         self.name, path = spec.split("=", 1)
-        self.fn = getattr(ctypes.CDLL(os.path.abspath(path)), _SYM)
+        lib = ctypes.CDLL(os.path.abspath(path))
+        self.doc_args = hasattr(lib, _SYM)
+        self.fn = getattr(lib, _SYM if self.doc_args else _SYM_NO_DOC)
         self.fn.restype = None
         self.fn.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [
-            ctypes.c_float, ctypes.c_bool, ctypes.c_bool, ctypes.c_void_p]
+            ctypes.c_float, ctypes.c_bool, ctypes.c_bool] + [
+            ctypes.c_void_p] * (3 if self.doc_args else 1)
 
     def __call__(self, p, out):
         B, Hq, S = p["q"].shape[0], p["q"].shape[1], p["q"].shape[2]
@@ -50,6 +57,7 @@ class Build:
                 p["dout"].data_ptr(), p["lse"].data_ptr(), p["delta"].data_ptr(),
                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
                 B, Hq, p["k"].shape[1], S, D ** -0.5, p["causal"], p["bshd"],
+                *((None, None) if self.doc_args else ()),
                 torch.cuda.current_stream().cuda_stream)
 
 

@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from torchft_amd.ops import RMSNorm, linear_cross_entropy, rope, rope_tables, swiglu_glu
-from torchft_amd.ops.flash_attention import flash_attention
+from torchft_amd.ops.flash_attention import DocMask, flash_attention
 
 
 _ENV_FUSED_CE = "TORCHFT_AMD_FUSED_CE"
@@ -84,7 +84,13 @@ class Attention(nn.Module):
         )
         self.wo = nn.Linear(cfg.n_heads * hd, d, bias=False, dtype=dtype)
 
-    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
+    def forward(
+        self,
+        x: torch.Tensor,
+        cos: torch.Tensor,
+        sin: torch.Tensor,
+        doc_mask: Optional[DocMask] = None,
+    ) -> torch.Tensor:
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
@@ -98,6 +104,10 @@ class Attention(nn.Module):
         q = rope(q, cos, sin)
         k = rope(k, cos, sin)
         if self.cp is not None and self.cp.world > 1:
+            if doc_mask is not None:
+                raise NotImplementedError(
+                    "doc_mask is not supported under context parallelism"
+                )
             from torchft_amd.parallel.cp import cp_attention
 
             out = cp_attention(
@@ -107,7 +117,7 @@ class Attention(nn.Module):
         # SDPA layout [B, H, S, D]; custom CDNA4 backward where enabled
         # (stock SDPA handles the transposed views without a copy)
         q, k, v = (t.transpose(1, 2) for t in (q, k, v))
-        out = flash_attention(q, k, v, causal=True)
+        out = flash_attention(q, k, v, causal=True, doc_mask=doc_mask)
         out = out.transpose(1, 2).reshape(B, S, -1)
         return self.wo(out)
 
@@ -133,8 +143,14 @@ class Block(nn.Module):
         self.mlp_norm = RMSNorm(cfg.dim, cfg.norm_eps, dtype=dtype)
         self.mlp = MLP(cfg, dtype)
 
-    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
-        x = x + self.attn(self.attn_norm(x), cos, sin)
+    def forward(
+        self,
+        x: torch.Tensor,
+        cos: torch.Tensor,
+        sin: torch.Tensor,
+        doc_mask: Optional[DocMask] = None,
+    ) -> torch.Tensor:
+        x = x + self.attn(self.attn_norm(x), cos, sin, doc_mask)
         x = x + self.mlp(self.mlp_norm(x))
         return x
 
@@ -172,11 +188,21 @@ class Llama(nn.Module):
             elif isinstance(m, nn.Embedding):
                 nn.init.normal_(m.weight, mean=0.0, std=std)
 
-    def forward_hidden(self, tokens: torch.Tensor) -> torch.Tensor:
+    def forward_hidden(
+        self, tokens: torch.Tensor, *, doc_mask: Optional[DocMask] = None
+    ) -> torch.Tensor:
         """Token ids [B, S] → final hidden states [B, S, dim].
 
         Under CP, ``tokens`` is this rank's contiguous sequence shard and
-        the rotary tables are sliced to its global positions."""
+        the rotary tables are sliced to its global positions.
+
+        ``doc_mask`` (packed rows, ``ops.DocMask``): attention stays causal
+        within each document. Rotary positions stay global: they do not
+        restart at document boundaries. Not supported under CP."""
+        if doc_mask is not None and self.cp is not None and self.cp.world > 1:
+            raise NotImplementedError(
+                "doc_mask is not supported under context parallelism"
+            )
         x = self.tok_embeddings(tokens)
         if self.cp is not None and self.cp.world > 1:
             s = tokens.shape[1]
@@ -187,15 +213,18 @@ class Llama(nn.Module):
         for layer in self.layers:
             if self.checkpoint_activations and self.training:
                 x = torch.utils.checkpoint.checkpoint(
-                    layer, x, cos, sin, use_reentrant=False
+                    layer, x, cos, sin, doc_mask, use_reentrant=False
                 )
             else:
-                x = layer(x, cos, sin)
+                x = layer(x, cos, sin, doc_mask)
         return self.norm(x)
 
-    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
-        """Full logits — use forward_loss for training (chunked CE)."""
-        return self.output(self.forward_hidden(tokens))
+    def forward(
+        self, tokens: torch.Tensor, *, doc_mask: Optional[DocMask] = None
+    ) -> torch.Tensor:
+        """Full logits — use forward_loss for training (chunked CE).
+        ``doc_mask``: see forward_hidden."""
+        return self.output(self.forward_hidden(tokens, doc_mask=doc_mask))
 
     def forward_loss(
         self,
@@ -206,6 +235,7 @@ class Llama(nn.Module):
         fused: Optional[bool] = None,
         ignore_index: int = -100,
         z_loss: float = 0.0,
+        doc_mask: Optional[DocMask] = None,
     ) -> torch.Tensor:
         """Mean cross-entropy with chunked logits: the [B*S, vocab] logits
         matrix (2 GB+ at 128k vocab) is computed ``chunk_rows`` rows at a
@@ -215,7 +245,10 @@ class Llama(nn.Module):
         the head through ``ops.linear_cross_entropy``: fp32 loss, memory
         bounded in training as well (the unfused loop keeps every chunk's
         bf16 log-probabilities alive until backward), and the only path
-        that supports ``ignore_index`` masking and ``z_loss``."""
+        that supports ``ignore_index`` masking and ``z_loss``.
+
+        ``doc_mask``: document-masked attention for packed rows, see
+        forward_hidden (global rotary positions)."""
         if fused is None:
             fused = fused_ce_enabled()
         if not fused and (ignore_index != -100 or z_loss != 0.0):
@@ -223,7 +256,7 @@ class Llama(nn.Module):
                 "ignore_index and z_loss need the fused cross-entropy head "
                 "(fused=True or TORCHFT_AMD_FUSED_CE=1)"
             )
-        h = self.forward_hidden(tokens)
+        h = self.forward_hidden(tokens, doc_mask=doc_mask)
         h = h.reshape(-1, self.cfg.dim)
         t = targets.reshape(-1)
         if fused:

@@ -512,3 +512,7 @@ from torchft_amd.ops.cross_entropy import linear_cross_entropy  # noqa: E402,F40
 # ----------------------------------------------------------------- DiLoCo outer sync
 
 from torchft_amd.ops.diloco import diloco_outer_step_, pseudograd_  # noqa: E402,F401
+
+# ----------------------------------------------------------------- Flash attention
+
+from torchft_amd.ops.flash_attention import DocMask, flash_attention  # noqa: E402,F401
