@@ -4,9 +4,11 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
+#include <c10/util/accumulate.h>
+
 #include <algorithm>
 #include <cmath>
-
+#include <cstdint>
 #include <vector>
 
 #include "fa_layout.h"
@@ -194,117 +196,208 @@ void fp8_dequantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
 }
 
 void fp8_reduce(at::Tensor recv, at::Tensor out, int64_t world, bool avg) {
-  TORCH_CHECK(recv.is_cuda() && out.is_cuda());
+  TORCH_CHECK(recv.is_cuda() && recv.scalar_type() == at::kByte && recv.is_contiguous(),
+              "fp8_reduce: recv must be a contiguous uint8 device tensor");
+  TORCH_CHECK(out.device() == recv.device() && out.scalar_type() == at::kByte &&
+                  out.is_contiguous(),
+              "fp8_reduce: out must be a contiguous uint8 tensor on recv's device");
   TORCH_CHECK(recv.numel() == out.numel() * world, "recv must hold world slices");
   const int64_t slice_bytes = out.numel();
   const int64_t blocks_per_rank = slice_bytes / (4 + tft::kMtBlock);
   TORCH_CHECK(blocks_per_rank * (4 + tft::kMtBlock) == slice_bytes, "bad slice size");
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
   tft::launch_reduce(recv.data_ptr<uint8_t>(), out.data_ptr<uint8_t>(), (int)world,
-                     blocks_per_rank, slice_bytes, avg, (tft_stream)stream);
+                     blocks_per_rank, slice_bytes, avg, current_stream());
 }
 
 // ---- fused model ops --------------------------------------------------------
 
+namespace {
+
+// The inputs of one RMSNorm / RoPE / SwiGLU call and the one rule they are
+// held to: every tensor is on the device of the first and has the dtype its
+// role asks for (bf16 activations, weights and gradients; fp32 invrms and
+// rotary tables). in() hands back what the kernel reads: made contiguous, and
+// copied to a fresh allocation if its first element is off a 16 B boundary
+// (the kernels use 16 B accesses), so nothing is refused for its layout.
+// Every refusal names the binding and the argument and comes before a launch;
+// the launchers start nothing for zero rows or elements.
+struct OpArgs {
+  const char* what;
+  at::Tensor first;  // x, a or gu, as the kernel reads it
+
+  OpArgs(const char* what_, const char* name, const at::Tensor& t) : what(what_) {
+    TORCH_CHECK(t.is_cuda(), what, ": ", name, " must be a device tensor");
+    TORCH_CHECK(t.dim() >= 1, what, ": ", name, " must have at least one dimension");
+    dev_ = t.device();
+    first = in(name, t, at::kBFloat16);
+  }
+
+  at::Tensor in(const char* name, const at::Tensor& t, at::ScalarType dtype) const {
+    TORCH_CHECK(t.device() == dev_, what, ": ", name, " must be on the device of the ",
+                "first tensor (", dev_, "), got ", t.device());
+    TORCH_CHECK(t.scalar_type() == dtype, what, ": ", name, " must be ", dtype, ", got ",
+                t.scalar_type());
+    at::Tensor c = t.contiguous();
+    if ((reinterpret_cast<uintptr_t>(c.data_ptr()) & 15) != 0) c = c.clone();
+    return c;
+  }
+  // a bf16 tensor of exactly these sizes
+  at::Tensor shaped(const char* name, const at::Tensor& t, at::IntArrayRef sizes) const {
+    TORCH_CHECK(t.sizes() == sizes, what, ": ", name, " must have the shape ", sizes,
+                ", got ", t.sizes());
+    return in(name, t, at::kBFloat16);
+  }
+  // a tensor of exactly `numel` elements, any shape
+  at::Tensor flat(const char* name, const at::Tensor& t, at::ScalarType dtype,
+                  int64_t numel) const {
+    TORCH_CHECK(t.numel() == numel, what, ": ", name, " must have ", numel,
+                " elements, got ", t.sizes());
+    return in(name, t, dtype);
+  }
+  // a size the kernels index with int and read 8 (or 4 pairs) at a time
+  int dim8(const char* name, int64_t v) const {
+    TORCH_CHECK(v % 8 == 0 && v < (int64_t(1) << 30), what, ": ", name,
+                " must be a multiple of 8 below 2^30, got ", v);
+    return (int)v;
+  }
+  void grid_ok(const char* name, int64_t grid) const {
+    TORCH_CHECK(grid < (int64_t(1) << 31), what, ": ", name,
+                " is too large for one launch (", grid, " workgroups)");
+  }
+  // elements per index of the last dimension
+  int64_t rows() const {
+    return c10::multiply_integers(first.sizes().slice(0, first.dim() - 1));
+  }
+
+ private:
+  at::Device dev_ = at::kCPU;
+};
+
+}  // namespace
+
 std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous());
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.is_contiguous());
-  const int H = (int)x.size(-1);
-  TORCH_CHECK(H % 8 == 0, "hidden dim must be a multiple of 8");
-  const int64_t rows = x.numel() / H;
-  auto y = at::empty_like(x);
-  auto invrms = at::empty({rows}, x.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
+  OpArgs a("rmsnorm_fwd", "x", x);
+  const int H = a.dim8("the last dimension of x (H)", a.first.size(-1));
+  const int64_t rows = a.rows();
+  a.grid_ok("x", rows);
+  auto wc = a.flat("w", w, at::kBFloat16, H);
+  auto y = at::empty_like(a.first);
+  auto invrms = at::empty({rows}, a.first.options().dtype(at::kFloat));
+  tft::launch_rmsnorm_fwd(a.first.data_ptr(), wc.data_ptr(), y.data_ptr(),
                           invrms.data_ptr<float>(), rows, H, (float)eps,
-                          (tft_stream)stream);
+                          current_stream());
   return {y, invrms};
 }
 
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                                     at::Tensor invrms) {
-  const int H = (int)x.size(-1);
-  const int64_t rows = x.numel() / H;
-  TORCH_CHECK(H * sizeof(float) <= 160 * 1024, "H too large for LDS dw buffer");
-  auto dx = at::empty_like(x);
-  auto dw = at::zeros({H}, x.options().dtype(at::kFloat));
-  auto dyc = dy.contiguous();
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_rmsnorm_bwd(dyc.data_ptr(), x.data_ptr(), w.data_ptr(),
-                          invrms.data_ptr<float>(), dx.data_ptr(),
-                          dw.data_ptr<float>(), rows, H, (tft_stream)stream);
+  OpArgs a("rmsnorm_bwd", "x", x);
+  const int H = a.dim8("the last dimension of x (H)", a.first.size(-1));
+  TORCH_CHECK(H * (int64_t)sizeof(float) <= tft::kRmsnormBwdMaxLdsBytes,
+              "rmsnorm_bwd: the last dimension of x (H) is too large for the LDS dw ",
+              "buffer, got ", H);
+  const int64_t rows = a.rows();
+  auto dyc = a.shaped("dy", dy, x.sizes());
+  auto wc = a.flat("w", w, at::kBFloat16, H);
+  auto invc = a.flat("invrms", invrms, at::kFloat, rows);
+  auto dx = at::empty_like(a.first);
+  auto dw = at::zeros({H}, a.first.options().dtype(at::kFloat));
+  tft::launch_rmsnorm_bwd(dyc.data_ptr(), a.first.data_ptr(), wc.data_ptr(),
+                          invc.data_ptr<float>(), dx.data_ptr(), dw.data_ptr<float>(),
+                          rows, H, current_stream());
   return {dx, dw};
 }
 
 at::Tensor rope_apply(at::Tensor x, at::Tensor cos_tab, at::Tensor sin_tab,
                       bool backward) {
   // x: [B, S, Hh, D]
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4);
-  auto xc = x.contiguous();
-  const int S = (int)x.size(1);
-  const int Hh = (int)x.size(2);
-  const int D = (int)x.size(3);
-  TORCH_CHECK(D % 8 == 0, "head dim must be a multiple of 8");
-  TORCH_CHECK(cos_tab.size(0) >= S && cos_tab.size(1) == D / 2, "cos table shape");
-  auto out = at::empty_like(xc);
-  const int64_t total_pairs = xc.numel() / 2;
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_rope(xc.data_ptr(), out.data_ptr(), cos_tab.data_ptr<float>(),
-                   sin_tab.data_ptr<float>(), total_pairs, S, Hh, D, backward,
-                   (tft_stream)stream);
+  OpArgs a("rope_apply", "x", x);
+  TORCH_CHECK(x.dim() == 4, "rope_apply: x must be 4-D [B, S, Hh, D], got ", x.sizes());
+  const int D = a.dim8("the last dimension of x (D)", x.size(3));
+  const int64_t S = x.size(1), Hh = x.size(2);
+  TORCH_CHECK(S < (int64_t(1) << 31) && Hh < (int64_t(1) << 31),
+              "rope_apply: x has too many positions or heads, got ", x.sizes());
+  TORCH_CHECK(cos_tab.dim() == 2 && cos_tab.size(0) >= S && cos_tab.size(1) == D / 2,
+              "rope_apply: cos_tab must be [at least ", S, ", ", D / 2, "], got ",
+              cos_tab.sizes());
+  TORCH_CHECK(sin_tab.sizes() == cos_tab.sizes(), "rope_apply: sin_tab must have the ",
+              "shape of cos_tab ", cos_tab.sizes(), ", got ", sin_tab.sizes());
+  auto cosc = a.in("cos_tab", cos_tab, at::kFloat);
+  auto sinc = a.in("sin_tab", sin_tab, at::kFloat);
+  const int64_t total_pairs = a.first.numel() / 2;
+  a.grid_ok("x", tft::elementwise_grid(total_pairs, 4));
+  auto out = at::empty_like(a.first);
+  tft::launch_rope(a.first.data_ptr(), out.data_ptr(), cosc.data_ptr<float>(),
+                   sinc.data_ptr<float>(), total_pairs, (int)S, (int)Hh, D, backward,
+                   current_stream());
   return out;
 }
 
+namespace {
+
+// a of the plain SwiGLU, its element count checked
+const at::Tensor& swiglu_a(const OpArgs& args) {
+  const int64_t n = args.first.numel();
+  TORCH_CHECK(n % 8 == 0, args.what, ": a must have a multiple of 8 elements, got ", n);
+  args.grid_ok("a", tft::elementwise_grid(n, 8));
+  return args.first;
+}
+
+// f of a packed gu = [..., 2f], checked
+int64_t glu_width(const OpArgs& a) {
+  const int64_t last = a.first.size(-1);
+  TORCH_CHECK(last % 2 == 0, a.what, ": the last dimension of gu must be even, got ", last);
+  TORCH_CHECK((last / 2) % 8 == 0, a.what, ": half the last dimension of gu (f) must be ",
+              "a multiple of 8, got ", last / 2);
+  a.grid_ok("gu", tft::elementwise_grid(a.first.numel() / 2, 8));
+  return last / 2;
+}
+
+}  // namespace
+
 at::Tensor swiglu_fwd(at::Tensor a, at::Tensor b) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(a.numel() % 8 == 0, "numel must be a multiple of 8");
-  auto ac = a.contiguous();
-  auto bc = b.contiguous();
+  OpArgs args("swiglu_fwd", "a", a);
+  const at::Tensor& ac = swiglu_a(args);
+  auto bc = args.shaped("b", b, a.sizes());
   auto out = at::empty_like(ac);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
   tft::launch_swiglu_fwd(ac.data_ptr(), bc.data_ptr(), out.data_ptr(), ac.numel(),
-                         (tft_stream)stream);
+                         current_stream());
   return out;
+}
+
+std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor a, at::Tensor b) {
+  OpArgs args("swiglu_bwd", "a", a);
+  const at::Tensor& ac = swiglu_a(args);
+  auto dyc = args.shaped("dy", dy, a.sizes());
+  auto bc = args.shaped("b", b, a.sizes());
+  auto da = at::empty_like(ac);
+  auto db = at::empty_like(bc);
+  tft::launch_swiglu_bwd(dyc.data_ptr(), ac.data_ptr(), bc.data_ptr(), da.data_ptr(),
+                         db.data_ptr(), ac.numel(), current_stream());
+  return {da, db};
 }
 
 at::Tensor swiglu_glu_fwd(at::Tensor gu) {
-  TORCH_CHECK(gu.is_cuda() && gu.scalar_type() == at::kBFloat16);
-  auto guc = gu.contiguous();
-  const int64_t f = guc.size(-1) / 2;
-  const int64_t rows = guc.numel() / (2 * f);
-  TORCH_CHECK(f % 8 == 0, "glu width must be a multiple of 8");
-  auto sizes = guc.sizes().vec();
+  OpArgs a("swiglu_glu_fwd", "gu", gu);
+  const int64_t f = glu_width(a);
+  auto sizes = a.first.sizes().vec();
   sizes.back() = f;
-  auto out = at::empty(sizes, guc.options());
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_swiglu_glu_fwd(guc.data_ptr(), out.data_ptr(), rows, f,
-                             (tft_stream)stream);
+  auto out = at::empty(sizes, a.first.options());
+  tft::launch_swiglu_glu_fwd(a.first.data_ptr(), out.data_ptr(), a.rows(), f,
+                             current_stream());
   return out;
 }
 
 at::Tensor swiglu_glu_bwd(at::Tensor dy, at::Tensor gu) {
-  auto dyc = dy.contiguous();
-  auto guc = gu.contiguous();
-  const int64_t f = guc.size(-1) / 2;
-  const int64_t rows = guc.numel() / (2 * f);
-  auto dgu = at::empty_like(guc);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_swiglu_glu_bwd(dyc.data_ptr(), guc.data_ptr(), dgu.data_ptr(),
-                             rows, f, (tft_stream)stream);
+  OpArgs a("swiglu_glu_bwd", "gu", gu);
+  const int64_t f = glu_width(a);
+  auto sizes = a.first.sizes().vec();
+  sizes.back() = f;
+  auto dyc = a.shaped("dy", dy, sizes);
+  auto dgu = at::empty_like(a.first);
+  tft::launch_swiglu_glu_bwd(dyc.data_ptr(), a.first.data_ptr(), dgu.data_ptr(), a.rows(), f,
+                             current_stream());
   return dgu;
-}
-
-std::vector<at::Tensor> swiglu_bwd(at::Tensor dy, at::Tensor a, at::Tensor b) {
-  auto dyc = dy.contiguous();
-  auto ac = a.contiguous();
-  auto bc = b.contiguous();
-  auto da = at::empty_like(ac);
-  auto db = at::empty_like(bc);
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
-  tft::launch_swiglu_bwd(dyc.data_ptr(), ac.data_ptr(), bc.data_ptr(),
-                         da.data_ptr(), db.data_ptr(), ac.numel(),
-                         (tft_stream)stream);
-  return {da, db};
 }
 
 // ---- fused AdamW ------------------------------------------------------------
@@ -722,11 +815,10 @@ at::Tensor cross_entropy_fwd_bwd(at::Tensor logits, at::Tensor targets,
               "all tensors must be on the same device");
   TORCH_CHECK(z_loss >= 0.0, "z_loss must be >= 0");
   auto row_loss = at::empty({R}, logits.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
   tft::launch_cross_entropy(logits.data_ptr(), targets.data_ptr<int64_t>(),
                             row_loss.data_ptr<float>(),
                             grad_scale.data_ptr<float>(), R, (int)V, ignore_index,
-                            (float)z_loss, write_grad, (tft_stream)stream);
+                            (float)z_loss, write_grad, current_stream());
   return row_loss;
 }
 
@@ -735,9 +827,8 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
   TORCH_CHECK(A.sizes() == at::IntArrayRef({32, 16}) &&
               B.sizes() == at::IntArrayRef({16, 32}));
   auto D = at::zeros({32, 32}, A.options().dtype(at::kFloat));
-  auto stream = at::cuda::getCurrentCUDAStream().stream();
   tft::launch_mfma_probe(A.contiguous().data_ptr(), B.contiguous().data_ptr(),
-                         D.data_ptr<float>(), (tft_stream)stream);
+                         D.data_ptr<float>(), current_stream());
   return D;
 }
 

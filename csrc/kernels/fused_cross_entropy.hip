@@ -30,34 +30,16 @@
 #include <cmath>
 #include <cstdint>
 
+#include "vec8.h"
+
 namespace torchft_amd {
 
 namespace {
 
 using bf16 = __hip_bfloat16;
-using bf16x2 = __hip_bfloat162;
 
 constexpr int kCeThreads = 1024;
 constexpr int kCeWaves = kCeThreads / 64;
-
-__device__ inline void ce_load_bf16x8(const bf16* p, float (&v)[8]) {
-  const uint4 raw = *reinterpret_cast<const uint4*>(p);
-  const bf16x2* h = reinterpret_cast<const bf16x2*>(&raw);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    float2 f = __bfloat1622float2(h[i]);
-    v[2 * i] = f.x;
-    v[2 * i + 1] = f.y;
-  }
-}
-
-__device__ inline void ce_store_bf16x8(bf16* p, const float (&v)[8]) {
-  uint4 raw;
-  bf16x2* h = reinterpret_cast<bf16x2*>(&raw);
-#pragma unroll
-  for (int i = 0; i < 4; i++) h[i] = __float22bfloat162_rn(make_float2(v[2 * i], v[2 * i + 1]));
-  *reinterpret_cast<uint4*>(p) = raw;
-}
 
 // (m, s) represents s * exp(m); the empty state is (-inf, 0). exp(-inf - m)
 // is 0 for finite m; the only NaN trap is -inf - -inf, guarded here.
@@ -113,7 +95,7 @@ cross_entropy_kernel(bf16* __restrict__ logits,
     if (tid == 0) row_loss[row] = 0.f;
     if (write_grad) {
       const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int i = tid; i < sp.nvec; i += kCeThreads) ce_store_bf16x8(xv + 8 * i, zero);
+      for (int i = tid; i < sp.nvec; i += kCeThreads) store8(xv + 8 * i, zero);
       if (tid < sp.nscalar) xr[ce_scalar_col(sp, tid)] = __float2bfloat16(0.f);
     }
     return;
@@ -129,7 +111,7 @@ cross_entropy_kernel(bf16* __restrict__ logits,
   float m = -INFINITY, s = 0.f;
   for (int i = tid; i < sp.nvec; i += kCeThreads) {
     float v[8];
-    ce_load_bf16x8(xv + 8 * i, v);
+    load8(xv + 8 * i, v);
     float vm = v[0];
 #pragma unroll
     for (int k = 1; k < 8; k++) vm = fmaxf(vm, v[k]);
@@ -181,14 +163,14 @@ cross_entropy_kernel(bf16* __restrict__ logits,
   const float coef = t_ok ? gs * (1.f + 2.f * z * lse) / s : NAN;
   for (int i = tid; i < sp.nvec; i += kCeThreads) {
     float v[8];
-    ce_load_bf16x8(xv + 8 * i, v);
+    load8(xv + 8 * i, v);
     const int col0 = sp.head + 8 * i;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const float g = coef * __expf(v[k] - m);
       v[k] = (col0 + k == tcol) ? g - gs : g;
     }
-    ce_store_bf16x8(xv + 8 * i, v);
+    store8(xv + 8 * i, v);
   }
   if (tid < sp.nscalar) {
     const int col = ce_scalar_col(sp, tid);

@@ -14,32 +14,15 @@
 
 #include <cstdint>
 
+#include "kernels.h"
+#include "vec8.h"
+
 namespace torchft_amd {
 
 using bf16 = __hip_bfloat16;
 using bf16x2 = __hip_bfloat162;
 
 // ---------------------------------------------------------------- helpers
-
-__device__ inline void load_bf16x8(const bf16* p, float (&v)[8]) {
-  // 8 bf16 = 16 bytes = one uint4 (ushort4 is only 8 bytes!)
-  const uint4 raw = *reinterpret_cast<const uint4*>(p);
-  const bf16x2* h = reinterpret_cast<const bf16x2*>(&raw);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    float2 f = __bfloat1622float2(h[i]);
-    v[2 * i] = f.x;
-    v[2 * i + 1] = f.y;
-  }
-}
-
-__device__ inline void store_bf16x8(bf16* p, const float (&v)[8]) {
-  uint4 raw;
-  bf16x2* h = reinterpret_cast<bf16x2*>(&raw);
-#pragma unroll
-  for (int i = 0; i < 4; i++) h[i] = __float22bfloat162_rn(make_float2(v[2 * i], v[2 * i + 1]));
-  *reinterpret_cast<uint4*>(p) = raw;
-}
 
 template <int THREADS>
 __device__ inline float block_reduce_sum(float v) {
@@ -75,7 +58,7 @@ __global__ void rmsnorm_fwd_kernel(const bf16* __restrict__ x,
   float ss = 0.f;
   for (int base = threadIdx.x * 8; base < H; base += THREADS * 8) {
     float v[8];
-    load_bf16x8(xr + base, v);
+    load8(xr + base, v);
 #pragma unroll
     for (int i = 0; i < 8; i++) ss += v[i] * v[i];
   }
@@ -85,18 +68,18 @@ __global__ void rmsnorm_fwd_kernel(const bf16* __restrict__ x,
 
   for (int base = threadIdx.x * 8; base < H; base += THREADS * 8) {
     float v[8], g[8];
-    load_bf16x8(xr + base, v);
-    load_bf16x8(w + base, g);
+    load8(xr + base, v);
+    load8(w + base, g);
 #pragma unroll
     for (int i = 0; i < 8; i++) v[i] = v[i] * inv * g[i];
-    store_bf16x8(yr + base, v);
+    store8(yr + base, v);
   }
 }
 
 // Grid-strided rows; per-block dw accumulated in LDS (fp32), one atomicAdd
 // sweep per block at the end. dw_out must be fp32 zeros [H].
 // dx = invrms * w * dy - (invrms^3 / H) * x * sum(dy*w*x)
-template <int THREADS, int MAX_H>
+template <int THREADS>
 __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
                                    const bf16* __restrict__ x,
                                    const bf16* __restrict__ w,
@@ -117,9 +100,9 @@ __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
     float s = 0.f;
     for (int base = threadIdx.x * 8; base < H; base += THREADS * 8) {
       float d[8], v[8], g[8];
-      load_bf16x8(dyr + base, d);
-      load_bf16x8(xr + base, v);
-      load_bf16x8(w + base, g);
+      load8(dyr + base, d);
+      load8(xr + base, v);
+      load8(w + base, g);
 #pragma unroll
       for (int i = 0; i < 8; i++) s += d[i] * g[i] * v[i];
     }
@@ -128,15 +111,15 @@ __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
 
     for (int base = threadIdx.x * 8; base < H; base += THREADS * 8) {
       float d[8], v[8], g[8], o[8];
-      load_bf16x8(dyr + base, d);
-      load_bf16x8(xr + base, v);
-      load_bf16x8(w + base, g);
+      load8(dyr + base, d);
+      load8(xr + base, v);
+      load8(w + base, g);
 #pragma unroll
       for (int i = 0; i < 8; i++) {
         o[i] = inv * g[i] * d[i] - k * v[i];
         dw_lds[base + i] += d[i] * v[i] * inv;
       }
-      store_bf16x8(dxr + base, o);
+      store8(dxr + base, o);
     }
     __syncthreads();  // dw_lds writes settle before next row reuses reduce LDS
   }
@@ -204,6 +187,26 @@ __global__ void rope_kernel(const bf16* __restrict__ x, bf16* __restrict__ out,
 
 // ---------------------------------------------------------------- SwiGLU
 
+// The element math, once for the plain and the packed kernels.
+// o = silu(a) * b
+__device__ inline void swiglu_fwd8(const float (&a)[8], const float (&b)[8],
+                                   float (&o)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const float sig = 1.f / (1.f + __expf(-a[i]));
+    o[i] = a[i] * sig * b[i];
+  }
+}
+
+// da = dy * b * sig(a) * (1 + a*(1-sig(a))) ; db = dy * a * sig(a). One
+// element: the kernels unroll it themselves (docs/KERNELS.md has why).
+__device__ inline void swiglu_bwd1(float dy, float a, float b, float& da, float& db) {
+  const float sig = 1.f / (1.f + __expf(-a));
+  const float silu = a * sig;
+  da = dy * b * sig * (1.f + a * (1.f - sig));
+  db = dy * silu;
+}
+
 // out = silu(a) * b ; elementwise, bf16x8.
 __global__ void swiglu_fwd_kernel(const bf16* __restrict__ a,
                                   const bf16* __restrict__ b,
@@ -211,17 +214,12 @@ __global__ void swiglu_fwd_kernel(const bf16* __restrict__ a,
   const int64_t base = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
   if (base >= n) return;
   float va[8], vb[8], vo[8];
-  load_bf16x8(a + base, va);
-  load_bf16x8(b + base, vb);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const float sig = 1.f / (1.f + __expf(-va[i]));
-    vo[i] = va[i] * sig * vb[i];
-  }
-  store_bf16x8(out + base, vo);
+  load8(a + base, va);
+  load8(b + base, vb);
+  swiglu_fwd8(va, vb, vo);
+  store8(out + base, vo);
 }
 
-// da = dy * b * sig(a) * (1 + a*(1-sig(a))) ; db = dy * a * sig(a)
 __global__ void swiglu_bwd_kernel(const bf16* __restrict__ dy,
                                   const bf16* __restrict__ a,
                                   const bf16* __restrict__ b,
@@ -230,18 +228,13 @@ __global__ void swiglu_bwd_kernel(const bf16* __restrict__ dy,
   const int64_t base = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
   if (base >= n) return;
   float vdy[8], va[8], vb[8], vda[8], vdb[8];
-  load_bf16x8(dy + base, vdy);
-  load_bf16x8(a + base, va);
-  load_bf16x8(b + base, vb);
+  load8(dy + base, vdy);
+  load8(a + base, va);
+  load8(b + base, vb);
 #pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const float sig = 1.f / (1.f + __expf(-va[i]));
-    const float silu = va[i] * sig;
-    vda[i] = vdy[i] * vb[i] * sig * (1.f + va[i] * (1.f - sig));
-    vdb[i] = vdy[i] * silu;
-  }
-  store_bf16x8(da + base, vda);
-  store_bf16x8(db + base, vdb);
+  for (int i = 0; i < 8; i++) swiglu_bwd1(vdy[i], va[i], vb[i], vda[i], vdb[i]);
+  store8(da + base, vda);
+  store8(db + base, vdb);
 }
 
 // Packed-GLU variants: gu = [rows][2f] with gate = gu[:, :f], up = gu[:, f:]
@@ -255,17 +248,13 @@ __global__ void swiglu_glu_fwd_kernel(const bf16* __restrict__ gu,
   const int64_t r = idx / f;
   const int64_t c = idx % f;
   float va[8], vb[8], vo[8];
-  load_bf16x8(gu + r * 2 * f + c, va);
-  load_bf16x8(gu + r * 2 * f + f + c, vb);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const float sig = 1.f / (1.f + __expf(-va[i]));
-    vo[i] = va[i] * sig * vb[i];
-  }
-  store_bf16x8(out + idx, vo);
+  load8(gu + r * 2 * f + c, va);
+  load8(gu + r * 2 * f + f + c, vb);
+  swiglu_fwd8(va, vb, vo);
+  store8(out + idx, vo);
 }
 
-// dgu (packed): dgate = dy * up * sig * (1 + gate*(1-sig)); dup = dy * silu
+// dgu (packed): dgate into gu's gate half, dup into its up half
 __global__ void swiglu_glu_bwd_kernel(const bf16* __restrict__ dy,
                                       const bf16* __restrict__ gu,
                                       bf16* __restrict__ dgu, int64_t rows,
@@ -275,24 +264,20 @@ __global__ void swiglu_glu_bwd_kernel(const bf16* __restrict__ dy,
   const int64_t r = idx / f;
   const int64_t c = idx % f;
   float vdy[8], va[8], vb[8], vda[8], vdb[8];
-  load_bf16x8(dy + idx, vdy);
-  load_bf16x8(gu + r * 2 * f + c, va);
-  load_bf16x8(gu + r * 2 * f + f + c, vb);
+  load8(dy + idx, vdy);
+  load8(gu + r * 2 * f + c, va);
+  load8(gu + r * 2 * f + f + c, vb);
 #pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const float sig = 1.f / (1.f + __expf(-va[i]));
-    const float silu = va[i] * sig;
-    vda[i] = vdy[i] * vb[i] * sig * (1.f + va[i] * (1.f - sig));
-    vdb[i] = vdy[i] * silu;
-  }
-  store_bf16x8(dgu + r * 2 * f + c, vda);
-  store_bf16x8(dgu + r * 2 * f + f + c, vdb);
+  for (int i = 0; i < 8; i++) swiglu_bwd1(vdy[i], va[i], vb[i], vda[i], vdb[i]);
+  store8(dgu + r * 2 * f + c, vda);
+  store8(dgu + r * 2 * f + f + c, vdb);
 }
 
 // ---------------------------------------------------------------- launchers
 
 void launch_rmsnorm_fwd(const void* x, const void* w, void* y, float* invrms,
                         int64_t rows, int H, float eps, hipStream_t stream) {
+  if (rows == 0) return;
   hipLaunchKernelGGL((rmsnorm_fwd_kernel<256>), dim3((uint32_t)rows), dim3(256), 0,
                      stream, (const bf16*)x, (const bf16*)w, (bf16*)y, invrms,
                      rows, H, eps);
@@ -301,56 +286,55 @@ void launch_rmsnorm_fwd(const void* x, const void* w, void* y, float* invrms,
 void launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                         const float* invrms, void* dx, float* dw, int64_t rows,
                         int H, hipStream_t stream) {
+  if (rows == 0) return;
   // grid: enough blocks to fill 256 CUs x ~4, capped so atomics stay cheap
   int grid = (int)(rows < 2048 ? rows : 2048);
-  size_t lds = (size_t)H * sizeof(float);
-  hipLaunchKernelGGL((rmsnorm_bwd_kernel<256, 8192>), dim3(grid), dim3(256), lds,
-                     stream, (const bf16*)dy, (const bf16*)x, (const bf16*)w,
-                     invrms, (bf16*)dx, dw, rows, H);
+  size_t lds = (size_t)H * sizeof(float);  // <= kRmsnormBwdMaxLdsBytes
+  hipLaunchKernelGGL((rmsnorm_bwd_kernel<256>), dim3(grid), dim3(256), lds, stream,
+                     (const bf16*)dy, (const bf16*)x, (const bf16*)w, invrms,
+                     (bf16*)dx, dw, rows, H);
+}
+
+// One lane per `per_lane` items, elementwise_grid workgroups of kElemThreads;
+// nothing to do, no launch.
+template <typename... P, typename... A>
+static void launch_elementwise(void (*kernel)(P...), int64_t items, int per_lane,
+                               hipStream_t stream, A... args) {
+  const int64_t grid = elementwise_grid(items, per_lane);
+  if (grid == 0) return;
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(kElemThreads), 0, stream,
+                     args...);
 }
 
 void launch_rope(const void* x, void* out, const float* cos_tab,
                  const float* sin_tab, int64_t total_pairs, int S, int Hh, int D,
                  bool backward, hipStream_t stream) {
-  const int threads = 256;
-  const int64_t work = (total_pairs + 4 * threads - 1) / (4 * threads);
-  hipLaunchKernelGGL(rope_kernel, dim3((uint32_t)work), dim3(threads), 0, stream,
-                     (const bf16*)x, (bf16*)out, cos_tab, sin_tab, total_pairs, S,
-                     Hh, D, backward ? -1.0f : 1.0f);
+  launch_elementwise(rope_kernel, total_pairs, 4, stream, (const bf16*)x, (bf16*)out,
+                     cos_tab, sin_tab, total_pairs, S, Hh, D, backward ? -1.0f : 1.0f);
 }
 
 void launch_swiglu_fwd(const void* a, const void* b, void* out, int64_t n,
                        hipStream_t stream) {
-  const int threads = 256;
-  const int64_t work = (n + 8 * threads - 1) / (8 * threads);
-  hipLaunchKernelGGL(swiglu_fwd_kernel, dim3((uint32_t)work), dim3(threads), 0,
-                     stream, (const bf16*)a, (const bf16*)b, (bf16*)out, n);
+  launch_elementwise(swiglu_fwd_kernel, n, 8, stream, (const bf16*)a, (const bf16*)b,
+                     (bf16*)out, n);
 }
 
 void launch_swiglu_bwd(const void* dy, const void* a, const void* b, void* da,
                        void* db, int64_t n, hipStream_t stream) {
-  const int threads = 256;
-  const int64_t work = (n + 8 * threads - 1) / (8 * threads);
-  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3((uint32_t)work), dim3(threads), 0,
-                     stream, (const bf16*)dy, (const bf16*)a, (const bf16*)b,
-                     (bf16*)da, (bf16*)db, n);
+  launch_elementwise(swiglu_bwd_kernel, n, 8, stream, (const bf16*)dy, (const bf16*)a,
+                     (const bf16*)b, (bf16*)da, (bf16*)db, n);
 }
 
 void launch_swiglu_glu_fwd(const void* gu, void* out, int64_t rows, int64_t f,
                            hipStream_t stream) {
-  const int threads = 256;
-  const int64_t work = (rows * f + 8 * threads - 1) / (8 * threads);
-  hipLaunchKernelGGL(swiglu_glu_fwd_kernel, dim3((uint32_t)work), dim3(threads),
-                     0, stream, (const bf16*)gu, (bf16*)out, rows, f);
+  launch_elementwise(swiglu_glu_fwd_kernel, rows * f, 8, stream, (const bf16*)gu,
+                     (bf16*)out, rows, f);
 }
 
 void launch_swiglu_glu_bwd(const void* dy, const void* gu, void* dgu,
                            int64_t rows, int64_t f, hipStream_t stream) {
-  const int threads = 256;
-  const int64_t work = (rows * f + 8 * threads - 1) / (8 * threads);
-  hipLaunchKernelGGL(swiglu_glu_bwd_kernel, dim3((uint32_t)work), dim3(threads),
-                     0, stream, (const bf16*)dy, (const bf16*)gu, (bf16*)dgu,
-                     rows, f);
+  launch_elementwise(swiglu_glu_bwd_kernel, rows * f, 8, stream, (const bf16*)dy,
+                     (const bf16*)gu, (bf16*)dgu, rows, f);
 }
 
 }  // namespace torchft_amd

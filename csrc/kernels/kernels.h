@@ -58,11 +58,23 @@ void launch_reduce(const uint8_t* in, uint8_t* out, int world,
                    tft_stream stream);
 
 // fused_model_ops.hip ------------------------------------------------------
+// bf16 activations, weights and gradients, fp32 invrms and rotary tables, all
+// contiguous and 16 B-aligned (the bindings see to both); H % 8 == 0,
+// D % 8 == 0, n % 8 == 0, f % 8 == 0. No rows or no elements: no launch.
 void launch_rmsnorm_fwd(const void* x, const void* w, void* y, float* invrms,
                         int64_t rows, int H, float eps, tft_stream stream);
+// a workgroup keeps its fp32 dw[H] in LDS: H * 4 <= kRmsnormBwdMaxLdsBytes;
+// dw must be zeros
+constexpr int64_t kRmsnormBwdMaxLdsBytes = 160 * 1024;
 void launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                         const float* invrms, void* dx, float* dw, int64_t rows,
                         int H, tft_stream stream);
+// The launchers below give every lane `per_lane` items (4 pairs, 8
+// elements) and a workgroup kElemThreads lanes. The grid must stay below 2^31.
+constexpr int kElemThreads = 256;
+constexpr int64_t elementwise_grid(int64_t items, int per_lane) {
+  return (items + per_lane * kElemThreads - 1) / (per_lane * kElemThreads);
+}
 void launch_rope(const void* x, void* out, const float* cos_tab,
                  const float* sin_tab, int64_t total_pairs, int S, int Hh, int D,
                  bool backward, tft_stream stream);
