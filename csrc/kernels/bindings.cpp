@@ -699,6 +699,16 @@ struct FaArgs {
   }
 
   const at::Tensor& q() const { return ts[0]; }
+  // nothing to compute: a zero batch or sequence. The launchers take no zero
+  // grid, so the bindings return their (empty) outputs unlaunched.
+  bool empty() const { return q().numel() == 0; }
+  // B * Hq is gridDim.y of the forward and dq launches; dkdv's B * Hkv is no
+  // larger, since k's heads divide q's
+  void check_grid() const {
+    const int64_t rows = q().size(0) * q().size(1);
+    TORCH_CHECK(rows <= tft::kFaMaxGridY, what, ": q has batch * heads = ", rows,
+                ", above the ", tft::kFaMaxGridY, " one launch covers");
+  }
   // tensor i as the kernels read it
   at::Tensor in(size_t i) const { return bshd ? ts[i] : ts[i].contiguous(); }
   // an uninitialized tensor of ts[i]'s logical shape in the resolved layout:
@@ -742,10 +752,11 @@ struct FaArgs {
 at::Tensor fa_delta(at::Tensor dout, at::Tensor out) {
   FaArgs a("fa_delta", "dout", dout, /*seq_multiple=*/1);
   a.add("out", out);
-  auto dc = a.in(0), oc = a.in(1);
   // delta is always dense [B, Hq, S]
   auto delta = at::empty({dout.size(0), dout.size(1), dout.size(2)},
                          dout.options().dtype(at::kFloat));
+  if (a.empty()) return delta;
+  auto dc = a.in(0), oc = a.in(1);
   tft::launch_fa_delta(dc.data_ptr(), oc.data_ptr(), delta.data_ptr<float>(),
                        dc.numel() / tft::kFaD, (int)dout.size(1), (int)dout.size(2),
                        a.bshd, current_stream());
@@ -759,9 +770,11 @@ std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   FaArgs a("fa_fwd", "q", q, /*seq_multiple=*/256);
   a.add_kv(k, v);
   a.add_doc(doc_start, doc_end, causal);
-  auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
+  a.check_grid();
   auto out = a.out_like(0);
   auto lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
+  if (a.empty()) return {out, lse};
+  auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
   tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
                      lse.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)k.size(1),
                      (int)q.size(2), (float)scale, causal, a.bshd, a.doc_start_ptr(),
@@ -778,9 +791,11 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   a.add_kv(k, v);
   a.add("dout", dout);
   a.add_doc(doc_start, doc_end, causal);
+  a.check_grid();
   auto lsec = a.stat("lse", lse), deltac = a.stat("delta", delta);
-  auto qc = a.in(0), kc = a.in(1), vc = a.in(2), doc = a.in(3);
   auto dq = a.out_like(0), dk = a.out_like(1), dv = a.out_like(2);
+  if (a.empty()) return {dq, dk, dv};
+  auto qc = a.in(0), kc = a.in(1), vc = a.in(2), doc = a.in(3);
   tft::launch_fa_bwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), doc.data_ptr(),
                      lsec.data_ptr<float>(), deltac.data_ptr<float>(), dq.data_ptr(),
                      dk.data_ptr(), dv.data_ptr(), (int)q.size(0), (int)q.size(1),

@@ -16,6 +16,8 @@ constexpr int kFaWaves = 8;      // wave64s per workgroup
 constexpr int kFaThreads = 512;
 constexpr int kFaBlk = 32;       // rows of one wave's block (one MFMA tile)
 static_assert(kFaThreads == kFaWaves * 64, "wave64");
+// the attention launches put batch * heads in gridDim.y
+constexpr int kFaMaxGridY = 65535;
 
 // One ROWS x 128 bf16 tile in LDS = 8 subtiles of [ROWS rows][16 cols], each
 // row-major and element-contiguous (tr_b16 needs its [4][16] blocks

@@ -8,24 +8,16 @@ import functools
 import pytest
 import torch
 
+from attention_check import DOC_LAYOUTS as LAYOUTS, doc_mask as _mask
+
 pytestmark = pytest.mark.gpu
 
 D = 128
 SCALE = D ** -0.5
-# the project's tolerances for these kernels (tests/test_flash_attn_gpu.py)
+# loose absolute tolerances shared with tests/test_flash_attn_gpu.py; the
+# derived bounds for two of these layouts: tests/test_flash_attn_numerics_gpu.py
 TOL_OUT, TOL_LSE, TOL_GRAD = 2e-2, 1e-3, 5e-2
 
-# B = 2 with different layouts in the two rows
-LAYOUTS = {
-    # boundaries inside a wave, on a 32 edge, on a 64 edge, a document of one
-    # token | rows 5-31 of wave 0 start a document inside its first block
-    "mixed256": (256, ([1, 31, 32, 33, 63, 96], [5, 251])),
-    "single256": (256, ([256], [1, 31, 32, 33, 63, 96])),
-    # two workgroups: the second skips the first's keys | a boundary inside
-    # the second workgroup
-    "halves512": (512, ([256, 256], [300, 212])),
-    "eighths512": (512, ([64] * 8, [300, 212])),
-}
 HEADS = [(2, 2), (8, 2)]
 
 
@@ -35,16 +27,11 @@ def _ext():
     return hip_ext()
 
 
-def _mask(name):
-    from torchft_amd.ops import DocMask
-
-    S, rows = LAYOUTS[name]
-    return DocMask.from_lengths(rows, S, device="cuda")
-
-
 def _close(what, got, ref, tol):
-    err = (got.double() - ref.double()).abs().max().item()
-    print(f"{what}: max abs err {err:.3e} (tolerance {tol:g})")
+    diff = (got.double() - ref.double()).abs()
+    ratio = (diff / (tol + tol * ref.double().abs())).max().item()
+    print(f"{what}: max abs err {diff.max().item():.3e}, worst ratio {ratio:.3f} "
+          f"of rtol = atol = {tol:g}")
     torch.testing.assert_close(got.double(), ref.double(), rtol=tol, atol=tol)
 
 

@@ -237,15 +237,37 @@ class TestRefusals:
 
 
 class TestFaDelta:
+    """fa_delta against fp64 of the same bf16 tensors under
+    depth * e * sum|d o| (docs/KERNELS.md, backward numerics)."""
+
     def test_delta_matches_torch(self):
+        self._check(0.0, False)
+
+    @pytest.mark.parametrize("offset,views", [(8.0, False), (0.0, True), (8.0, True)],
+                             ids=["plus8-packed", "zero_mean-bshd", "plus8-bshd"])
+    def test_delta_offset_and_views(self, offset, views):
+        """An `out` with the +8 offset that makes delta large, and
+        [B,S,H,D]-backed views."""
+        self._check(offset, views)
+
+    @staticmethod
+    def _check(offset, views):
+        import attention_check as ac
         from torchft_amd.ops import hip_ext
 
         torch.manual_seed(23)
-        d = torch.randn(2, 4, 256, 128, device="cuda", dtype=torch.bfloat16)
-        o = torch.randn_like(d)
+        B, H, S = 2, 4, 256
+        shape = (B, S, H, 128) if views else (B, H, S, 128)
+        d = torch.randn(shape, device="cuda", dtype=torch.bfloat16)
+        o = (torch.randn(shape, device="cuda") + offset).to(torch.bfloat16)
+        if views:
+            d, o = d.transpose(1, 2), o.transpose(1, 2)
         got = hip_ext().fa_delta(d, o)
-        ref = (d.float() * o.float()).sum(-1)
-        torch.testing.assert_close(got, ref, rtol=2e-2, atol=2e-2)
+        assert got.shape == (B, H, S) and got.is_contiguous()
+        assert torch.isfinite(got).all()
+        ratio = ac.delta_ratio(got, d, o)
+        print(f"fa_delta offset {offset} views {views}: {ratio:.3f} of the bound")
+        assert ratio <= 1.0
 
 
 class TestBshdLayout:
