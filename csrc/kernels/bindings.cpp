@@ -28,7 +28,8 @@ struct PackGeom {
   int64_t slice_bytes = 0;
 };
 
-PackGeom pack_geometry(const TensorList& tensors, int64_t world) {
+PackGeom pack_geometry(const TensorList& tensors, int64_t world, const char* what) {
+  TORCH_CHECK(world >= 1, what, ": world must be >= 1, got ", world);
   PackGeom g;
   for (auto& t : tensors) g.total_blocks += (t.numel() + tft::kMtBlock - 1) / tft::kMtBlock;
   g.padded_blocks = ((g.total_blocks + world - 1) / world) * world;
@@ -144,6 +145,21 @@ class TableSet {
   at::Tensor dev_words_;
 };
 
+// The wire buffer of a quantize / dequantize call: contiguous uint8 on the
+// tensors' device, large enough for every slice. A host `pack` would hand the
+// kernel a host pointer, a short one lets it run past the end.
+void check_pack(const at::Tensor& pack, const TensorList& tensors, const PackGeom& g,
+                int64_t world, const char* what) {
+  TORCH_CHECK(pack.scalar_type() == at::kByte, what, ": pack must be uint8, got ",
+              pack.scalar_type());
+  TORCH_CHECK(pack.is_cuda() && pack.device() == tensors[0].device(), what,
+              ": pack must be on the tensors' device (", tensors[0].device(), "), got ",
+              pack.device());
+  TORCH_CHECK(pack.is_contiguous(), what, ": pack must be contiguous");
+  TORCH_CHECK(pack.numel() >= g.slice_bytes * world, what, ": pack holds ", pack.numel(),
+              " bytes, needs ", g.slice_bytes * world);
+}
+
 // dtype_code of a call whose tensors all share the dtype of the first; the
 // table's checks hold the others to it
 int first_dtype_code(const TensorList& tensors, const char* what) {
@@ -163,19 +179,20 @@ tft_stream current_stream() {
 // table: col 0 = the tensors, all of the first one's dtype and 16 B-aligned
 
 int64_t fp8_pack_bytes(const std::vector<at::Tensor>& tensors, int64_t world) {
-  auto g = pack_geometry(tensors, world);
+  auto g = pack_geometry(tensors, world, "fp8_pack_bytes");
   return g.slice_bytes * world;
 }
 
 int64_t fp8_slice_bytes(const std::vector<at::Tensor>& tensors, int64_t world) {
-  return pack_geometry(tensors, world).slice_bytes;
+  return pack_geometry(tensors, world, "fp8_slice_bytes").slice_bytes;
 }
 
 void fp8_quantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
                   int64_t world) {
   const int code = first_dtype_code(tensors, "fp8_quantize");
-  auto g = pack_geometry(tensors, world);
-  TORCH_CHECK(pack.numel() >= g.slice_bytes * world, "pack buffer too small");
+  TORCH_CHECK(tensors[0].is_cuda(), "fp8_quantize: requires device tensors");
+  auto g = pack_geometry(tensors, world, "fp8_quantize");
+  check_pack(pack, tensors, g, world, "fp8_quantize");
   TableSet tables(tensors[0], "fp8_quantize", /*need_16b_alignment=*/true);
   const int h = tables.add({{&tensors, tensors[0].scalar_type()}});
   tables.upload();
@@ -186,7 +203,9 @@ void fp8_quantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
 void fp8_dequantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
                     int64_t world) {
   const int code = first_dtype_code(tensors, "fp8_dequantize");
-  auto g = pack_geometry(tensors, world);
+  TORCH_CHECK(tensors[0].is_cuda(), "fp8_dequantize: requires device tensors");
+  auto g = pack_geometry(tensors, world, "fp8_dequantize");
+  check_pack(pack, tensors, g, world, "fp8_dequantize");
   TableSet tables(tensors[0], "fp8_dequantize", /*need_16b_alignment=*/true);
   const int h = tables.add({{&tensors, tensors[0].scalar_type()}});
   tables.upload();
@@ -201,10 +220,14 @@ void fp8_reduce(at::Tensor recv, at::Tensor out, int64_t world, bool avg) {
   TORCH_CHECK(out.device() == recv.device() && out.scalar_type() == at::kByte &&
                   out.is_contiguous(),
               "fp8_reduce: out must be a contiguous uint8 tensor on recv's device");
-  TORCH_CHECK(recv.numel() == out.numel() * world, "recv must hold world slices");
+  TORCH_CHECK(world >= 1, "fp8_reduce: world must be >= 1, got ", world);
+  TORCH_CHECK(recv.numel() == out.numel() * world,
+              "fp8_reduce: recv must hold world slices of out's size");
   const int64_t slice_bytes = out.numel();
   const int64_t blocks_per_rank = slice_bytes / (4 + tft::kMtBlock);
-  TORCH_CHECK(blocks_per_rank * (4 + tft::kMtBlock) == slice_bytes, "bad slice size");
+  TORCH_CHECK(blocks_per_rank * (4 + tft::kMtBlock) == slice_bytes,
+              "fp8_reduce: out is not a whole number of blocks");
+  if (blocks_per_rank == 0) return;  // nothing but empty tensors: no launch
   tft::launch_reduce(recv.data_ptr<uint8_t>(), out.data_ptr<uint8_t>(), (int)world,
                      blocks_per_rank, slice_bytes, avg, current_stream());
 }

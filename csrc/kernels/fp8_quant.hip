@@ -46,6 +46,23 @@ __device__ inline float block_reduce_max(float v) {
   return m;  // every thread gets the block max
 }
 
+// ---- block scales ----------------------------------------------------------
+
+// q = 448/amax maps the block onto the e4m3 range, dq = amax/448 is what goes
+// on the wire. A block of zeros gets 0 / 0. So does a block whose amax is
+// below 448/FLT_MAX (1.3e-36, every fp32 subnormal included): 448/amax
+// overflows to +inf there, and inf times the block's values would be inf or,
+// for its zeros, NaN, so finite input would leave the wire as NaN. Such a
+// block is flushed to zero instead. amax = +inf (an Inf element) keeps q = 0,
+// dq = inf: the block decodes to NaN everywhere. A NaN element never enters
+// amax (fmaxf returns the other operand) and stays NaN through NaN * q.
+__device__ inline void block_scales(float amax, float inv_div, float& q_scale,
+                                    float& dq_scale) {
+  q_scale = amax > 0.f ? (FP8_MAX / amax) : 0.f;
+  dq_scale = amax > 0.f ? (amax / FP8_MAX) * inv_div : 0.f;
+  if (isinf(q_scale)) q_scale = dq_scale = 0.f;
+}
+
 // ---- quantize --------------------------------------------------------------
 
 // These two kernels move only 6 KB per workgroup, so their time is set by the
@@ -97,8 +114,8 @@ __global__ void quantize_fp8_kernel(
   for (int i = 0; i < kMtEpt; i++) amax = fmaxf(amax, fabsf(v[i]));
   amax = block_reduce_max(amax);
 
-  const float q_scale = amax > 0.f ? (FP8_MAX / amax) : 0.f;
-  const float dq_scale = amax > 0.f ? (amax / FP8_MAX) : 0.f;
+  float q_scale, dq_scale;
+  block_scales(amax, 1.f, q_scale, dq_scale);
 
   uint8_t q[8];
 #pragma unroll
@@ -183,10 +200,10 @@ __global__ void reduce_fp8_slices_kernel(const uint8_t* __restrict__ in,
   for (int i = 0; i < kMtEpt; i++) amax = fmaxf(amax, fabsf(acc[i]));
   amax = block_reduce_max(amax);
 
-  const float q_scale = amax > 0.f ? (FP8_MAX / amax) : 0.f;
   // inv_div folds AVG's 1/world into the stored dequant scale — the payload
   // bytes are identical for SUM and AVG.
-  const float dq_scale = amax > 0.f ? (amax / FP8_MAX) * inv_div : 0.f;
+  float q_scale, dq_scale;
+  block_scales(amax, inv_div, q_scale, dq_scale);
 
   float* scale_out = reinterpret_cast<float*>(out) + bl;
   uint8_t* payload_out = out + blocks_per_rank * 4 + bl * kMtBlock;
@@ -231,6 +248,7 @@ void launch_dequantize_dtype(int dtype_code, MultiTensorTable tb,
 void launch_reduce(const uint8_t* in, uint8_t* out, int world,
                    int64_t blocks_per_rank, int64_t slice_bytes, bool avg,
                    hipStream_t stream) {
+  if (blocks_per_rank <= 0 || world <= 0) return;
   hipLaunchKernelGGL(reduce_fp8_slices_kernel, dim3((uint32_t)blocks_per_rank),
                      dim3(kMtThreads), 0, stream, in, out, world, blocks_per_rank,
                      slice_bytes, avg ? 1.0f / world : 1.0f);
