@@ -14,6 +14,7 @@
 #include "fa_layout.h"
 #include "kernels.h"
 #include "multi_tensor_host.h"
+#include "qkv_layout.h"
 
 namespace tft = torchft_amd;
 
@@ -236,7 +237,7 @@ void fp8_reduce(at::Tensor recv, at::Tensor out, int64_t world, bool avg) {
 
 namespace {
 
-// The inputs of one RMSNorm / RoPE / SwiGLU call and the one rule they are
+// The inputs of one RMSNorm / RoPE / SwiGLU / QKV-split call and the one rule they are
 // held to: every tensor is on the device of the first and has the dtype its
 // role asks for (bf16 activations, weights and gradients; fp32 invrms and
 // rotary tables). in() hands back what the kernel reads: made contiguous, and
@@ -421,6 +422,110 @@ at::Tensor swiglu_glu_bwd(at::Tensor dy, at::Tensor gu) {
   tft::launch_swiglu_glu_bwd(dyc.data_ptr(), a.first.data_ptr(), dgu.data_ptr(), a.rows(), f,
                              current_stream());
   return dgu;
+}
+
+// ---- fused QKV split + rotary ---------------------------------------------------
+
+namespace {
+
+// What qkv_rope_fwd and qkv_rope_bwd share once the activations are known: the
+// head dimension, the rotary tables (rope_apply's rule, with one row enough
+// when `positions` picks the rows), the optional per-token positions, and the
+// grid.
+struct QkvRopeArgs {
+  int D = 0;
+  int table_rows = 0;
+  at::Tensor cos, sin, positions;
+
+  // name: the activation the sizes come from (qkv or dq); Hq, Hkv below 2^30
+  QkvRopeArgs(const OpArgs& a, const char* name, int64_t B, int64_t S, int64_t Hq,
+              int64_t Hkv, int64_t D_, const at::Tensor& cos_tab,
+              const at::Tensor& sin_tab, const c10::optional<at::Tensor>& pos) {
+    TORCH_CHECK(D_ >= 16 && D_ % 16 == 0 && D_ < (int64_t(1) << 30), a.what,
+                ": the head dimension of ", name, " (D) must be a multiple of 16 below ",
+                "2^30, got ", D_);
+    D = (int)D_;
+    TORCH_CHECK(S < (int64_t(1) << 31) && (Hq + 2 * Hkv) * D_ < (int64_t(1) << 31), a.what,
+                ": ", name, " has too many positions or too wide a row, got S = ", S,
+                ", W = ", (Hq + 2 * Hkv) * D_);
+    const int64_t min_rows = pos.has_value() ? 1 : S;
+    TORCH_CHECK(cos_tab.dim() == 2 && cos_tab.size(0) >= min_rows &&
+                    cos_tab.size(1) == D / 2,
+                a.what, ": cos_tab must be [at least ", min_rows, ", ", D / 2, "], got ",
+                cos_tab.sizes());
+    TORCH_CHECK(sin_tab.sizes() == cos_tab.sizes(), a.what, ": sin_tab must have the ",
+                "shape of cos_tab ", cos_tab.sizes(), ", got ", sin_tab.sizes());
+    cos = a.in("cos_tab", cos_tab, at::kFloat);
+    sin = a.in("sin_tab", sin_tab, at::kFloat);
+    // the kernels clamp a position into [0, table_rows - 1] as an int; with
+    // no rows (and so no tokens) nothing is launched
+    table_rows = (int)std::min<int64_t>(cos_tab.size(0), INT32_MAX);
+    if (pos.has_value()) {
+      TORCH_CHECK(pos->is_cuda(), a.what, ": positions must be a device tensor");
+      positions = a.flat("positions", *pos, at::kInt, B * S);
+    }
+    const int64_t items = B * S * tft::qkv_items_per_token((int)Hq, (int)Hkv, D);
+    a.grid_ok(name, tft::elementwise_grid(items, 1));
+  }
+
+  const int* positions_ptr() const {
+    return positions.defined() ? positions.data_ptr<int>() : nullptr;
+  }
+};
+
+}  // namespace
+
+// qkv [B, S, (n_heads + 2 * n_kv_heads) * D] -> q [B, S, n_heads, D] and
+// k, v [B, S, n_kv_heads, D], q and k rotated; positions: int32, B * S
+// elements, the table row of every token (row s without it).
+std::vector<at::Tensor> qkv_rope_fwd(at::Tensor qkv, at::Tensor cos_tab, at::Tensor sin_tab,
+                                     int64_t n_heads, int64_t n_kv_heads,
+                                     c10::optional<at::Tensor> positions) {
+  OpArgs a("qkv_rope_fwd", "qkv", qkv);
+  TORCH_CHECK(qkv.dim() == 3, "qkv_rope_fwd: qkv must be 3-D [B, S, W], got ", qkv.sizes());
+  TORCH_CHECK(n_heads >= 1, "qkv_rope_fwd: n_heads must be >= 1, got ", n_heads);
+  TORCH_CHECK(n_kv_heads >= 1, "qkv_rope_fwd: n_kv_heads must be >= 1, got ", n_kv_heads);
+  const int64_t B = qkv.size(0), S = qkv.size(1), W = qkv.size(2);
+  TORCH_CHECK(n_heads < (int64_t(1) << 30) && n_kv_heads < (int64_t(1) << 30) &&
+                  W % (n_heads + 2 * n_kv_heads) == 0,
+              "qkv_rope_fwd: the last dimension of qkv (W = ", W, ") must be divisible by ",
+              "n_heads + 2 * n_kv_heads = ", n_heads, " + 2 * ", n_kv_heads);
+  QkvRopeArgs r(a, "qkv", B, S, n_heads, n_kv_heads, W / (n_heads + 2 * n_kv_heads),
+                cos_tab, sin_tab, positions);
+  auto q = at::empty({B, S, n_heads, r.D}, a.first.options());
+  auto k = at::empty({B, S, n_kv_heads, r.D}, a.first.options());
+  auto v = at::empty({B, S, n_kv_heads, r.D}, a.first.options());
+  tft::launch_qkv_rope_fwd(a.first.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                           r.cos.data_ptr<float>(), r.sin.data_ptr<float>(),
+                           r.positions_ptr(), r.table_rows, B * S, (int)S, (int)n_heads,
+                           (int)n_kv_heads, r.D, current_stream());
+  return {q, k, v};
+}
+
+// The transpose: dq [B, S, Hq, D], dk and dv [B, S, Hkv, D] ->
+// dqkv [B, S, (Hq + 2 * Hkv) * D], every element written.
+at::Tensor qkv_rope_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor cos_tab,
+                        at::Tensor sin_tab, c10::optional<at::Tensor> positions) {
+  OpArgs a("qkv_rope_bwd", "dq", dq);
+  TORCH_CHECK(dq.dim() == 4, "qkv_rope_bwd: dq must be 4-D [B, S, Hq, D], got ", dq.sizes());
+  const int64_t B = dq.size(0), S = dq.size(1), Hq = dq.size(2), D = dq.size(3);
+  TORCH_CHECK(Hq >= 1, "qkv_rope_bwd: dq must have at least one head, got ", dq.sizes());
+  TORCH_CHECK(dk.dim() == 4 && dk.size(0) == B && dk.size(1) == S && dk.size(2) >= 1 &&
+                  dk.size(3) == D,
+              "qkv_rope_bwd: dk must be [B, S, Hkv, D] with dq's B, S and D, got ",
+              dk.sizes(), " against ", dq.sizes());
+  const int64_t Hkv = dk.size(2);
+  TORCH_CHECK(Hq < (int64_t(1) << 30) && Hkv < (int64_t(1) << 30),
+              "qkv_rope_bwd: dq or dk has too many heads");
+  QkvRopeArgs r(a, "dq", B, S, Hq, Hkv, D, cos_tab, sin_tab, positions);
+  auto dkc = a.in("dk", dk, at::kBFloat16);
+  auto dvc = a.shaped("dv", dv, dk.sizes());
+  auto dqkv = at::empty({B, S, (Hq + 2 * Hkv) * D}, a.first.options());
+  tft::launch_qkv_rope_bwd(a.first.data_ptr(), dkc.data_ptr(), dvc.data_ptr(),
+                           dqkv.data_ptr(), r.cos.data_ptr<float>(),
+                           r.sin.data_ptr<float>(), r.positions_ptr(), r.table_rows, B * S,
+                           (int)S, (int)Hq, (int)Hkv, r.D, current_stream());
+  return dqkv;
 }
 
 // ---- fused AdamW ------------------------------------------------------------
@@ -884,6 +989,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_glu_fwd", &swiglu_glu_fwd);
   m.def("swiglu_glu_bwd", &swiglu_glu_bwd);
   m.def("swiglu_bwd", &swiglu_bwd);
+  m.def("qkv_rope_fwd", &qkv_rope_fwd, py::arg("qkv"), py::arg("cos_tab"),
+        py::arg("sin_tab"), py::arg("n_heads"), py::arg("n_kv_heads"),
+        py::arg("positions") = py::none(),
+        "fused QKV split + rotary: returns [q, k, v], contiguous [B, S, H, D]");
+  m.def("qkv_rope_bwd", &qkv_rope_bwd, py::arg("dq"), py::arg("dk"), py::arg("dv"),
+        py::arg("cos_tab"), py::arg("sin_tab"), py::arg("positions") = py::none(),
+        "transpose of qkv_rope_fwd: returns dqkv [B, S, (Hq + 2 * Hkv) * D]");
   m.def("adamw_step", &adamw_step);
   m.def("adamw_clip_step", &adamw_clip_step,
         "FusedAdamW step with fused global-norm clip and non-finite skip");

@@ -87,6 +87,24 @@ void launch_swiglu_glu_bwd(const void* dy, const void* gu, void* dgu,
 void launch_swiglu_bwd(const void* dy, const void* a, const void* b, void* da,
                        void* db, int64_t n, tft_stream stream);
 
+// qkv_rope.hip ---------------------------------------------------------------
+// Fused split + rotary of the QKV projection (qkv_layout.h has the map).
+// qkv / dqkv: bf16 [tokens, (Hq + 2*Hkv) * D]; q / dq: [tokens, Hq, D]; k, v /
+// dk, dv: [tokens, Hkv, D]; tokens = B * S. All contiguous and 16 B-aligned,
+// D % 16 == 0. cos / sin: fp32 [table_rows, D/2], table_rows >= 1. positions:
+// int32 [tokens] on the device, or null for position s = token % S (then
+// table_rows >= S). One lane per 16 elements, elementwise_grid(items, 1)
+// workgroups (below 2^31); no tokens, no launch. The backward writes every
+// element of dqkv.
+void launch_qkv_rope_fwd(const void* qkv, void* q, void* k, void* v,
+                         const float* cos_tab, const float* sin_tab,
+                         const int* positions, int table_rows, int64_t tokens, int S,
+                         int Hq, int Hkv, int D, tft_stream stream);
+void launch_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, void* dqkv,
+                         const float* cos_tab, const float* sin_tab,
+                         const int* positions, int table_rows, int64_t tokens, int S,
+                         int Hq, int Hkv, int D, tft_stream stream);
+
 // fused_adamw.hip ----------------------------------------------------------
 // table: cols 0..3 = param, grad, exp_avg, exp_avg_sq (bf16, bf16, fp32, fp32)
 void launch_adamw(MultiTensorTable tb, float lr, float beta1, float beta2,

@@ -18,11 +18,19 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from torchft_amd.ops import RMSNorm, linear_cross_entropy, rope, rope_tables, swiglu_glu
+from torchft_amd.ops import (
+    RMSNorm,
+    linear_cross_entropy,
+    qkv_rope,
+    rope,
+    rope_tables,
+    swiglu_glu,
+)
 from torchft_amd.ops.flash_attention import DocMask, flash_attention
 
 
 _ENV_FUSED_CE = "TORCHFT_AMD_FUSED_CE"
+_ENV_FUSED_QKV_ROPE = "TORCHFT_AMD_FUSED_QKV_ROPE"
 
 
 def fused_ce_enabled() -> bool:
@@ -30,6 +38,15 @@ def fused_ce_enabled() -> bool:
     numerics from bf16-rounded to fp32)."""
     v = os.environ.get(_ENV_FUSED_CE, "0")
     return v in ("1", "true", "True")
+
+
+def fused_qkv_rope_enabled() -> bool:
+    """The fused QKV split + rotary kernel (``ops.qkv_rope``) in
+    ``Attention.forward`` on a HIP device; TORCHFT_AMD_FUSED_QKV_ROPE=0 takes
+    the three views and two ``rope`` calls instead. Both give the same bits
+    (docs/KERNELS.md, "qkv_rope.hip"); the flag is there so that the two paths
+    can be alternated under one benchmark."""
+    return os.environ.get(_ENV_FUSED_QKV_ROPE, "1") != "0"
 
 
 @dataclass
@@ -53,6 +70,9 @@ class LlamaConfig:
     max_seq_len: int = 8192
     rope_theta: float = 500000.0
     norm_eps: float = 1e-5
+    # with a doc_mask, rotary positions restart at 0 at every document start
+    # (DocMask.positions()); False keeps them global along the packed row
+    rope_doc_reset: bool = False
 
     @property
     def head_dim(self) -> int:
@@ -90,19 +110,34 @@ class Attention(nn.Module):
         cos: torch.Tensor,
         sin: torch.Tensor,
         doc_mask: Optional[DocMask] = None,
+        positions: Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
+        """``positions`` (int32 [B, S], ``DocMask.positions()``): the rotary
+        table row of every token; None rotates token ``s`` by row ``s``."""
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
         qkv = self.wqkv(x)
-        nq = cfg.n_heads * hd
-        nkv = cfg.n_kv_heads * hd
-        q = qkv[..., :nq].view(B, S, cfg.n_heads, hd)
-        k = qkv[..., nq : nq + nkv].view(B, S, cfg.n_kv_heads, hd)
-        v = qkv[..., nq + nkv :].view(B, S, cfg.n_kv_heads, hd)
-        # cos/sin already sliced to this rank's global positions under CP
-        q = rope(q, cos, sin)
-        k = rope(k, cos, sin)
+        # One kernel splits and rotates (contiguous q, k, v, which attention
+        # then takes without a layout copy). Per-token positions exist only
+        # there, so with them it runs whatever the flag says; without them it
+        # runs where the kernel applies.
+        if positions is not None or (
+            qkv.is_cuda
+            and qkv.dtype == torch.bfloat16
+            and hd % 16 == 0
+            and fused_qkv_rope_enabled()
+        ):
+            q, k, v = qkv_rope(qkv, cos, sin, cfg.n_heads, cfg.n_kv_heads, positions)
+        else:
+            nq = cfg.n_heads * hd
+            nkv = cfg.n_kv_heads * hd
+            q = qkv[..., :nq].view(B, S, cfg.n_heads, hd)
+            k = qkv[..., nq : nq + nkv].view(B, S, cfg.n_kv_heads, hd)
+            v = qkv[..., nq + nkv :].view(B, S, cfg.n_kv_heads, hd)
+            # cos/sin already sliced to this rank's global positions under CP
+            q = rope(q, cos, sin)
+            k = rope(k, cos, sin)
         if self.cp is not None and self.cp.world > 1:
             if doc_mask is not None:
                 raise NotImplementedError(
@@ -149,8 +184,9 @@ class Block(nn.Module):
         cos: torch.Tensor,
         sin: torch.Tensor,
         doc_mask: Optional[DocMask] = None,
+        positions: Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
-        x = x + self.attn(self.attn_norm(x), cos, sin, doc_mask)
+        x = x + self.attn(self.attn_norm(x), cos, sin, doc_mask, positions)
         x = x + self.mlp(self.mlp_norm(x))
         return x
 
@@ -164,6 +200,11 @@ class Llama(nn.Module):
         cp: Optional[CPPlan] = None,
     ) -> None:
         super().__init__()
+        if cfg.rope_doc_reset and cfg.head_dim % 16 != 0:
+            raise ValueError(
+                f"rope_doc_reset needs head_dim % 16 == 0 (the fused QKV + rotary "
+                f"kernel's item size), got head_dim = {cfg.head_dim}"
+            )
         self.cfg = cfg
         self.cp = cp
         self.checkpoint_activations = checkpoint_activations
@@ -197,8 +238,12 @@ class Llama(nn.Module):
         the rotary tables are sliced to its global positions.
 
         ``doc_mask`` (packed rows, ``ops.DocMask``): attention stays causal
-        within each document. Rotary positions stay global: they do not
-        restart at document boundaries. Not supported under CP."""
+        within each document. Rotary positions stay global by default: they
+        do not restart at document boundaries. With
+        ``LlamaConfig.rope_doc_reset`` they restart at 0 at every document
+        start (``doc_mask.positions()``), so a packed document sees the
+        rotations it would see alone; without a ``doc_mask`` the setting
+        changes nothing. Not supported under CP."""
         if doc_mask is not None and self.cp is not None and self.cp.world > 1:
             raise NotImplementedError(
                 "doc_mask is not supported under context parallelism"
@@ -210,13 +255,19 @@ class Llama(nn.Module):
             cos, sin = self.rope_cos[off : off + s], self.rope_sin[off : off + s]
         else:
             cos, sin = self.rope_cos, self.rope_sin
+        # once per batch, shared by every layer
+        positions = (
+            doc_mask.positions()
+            if doc_mask is not None and self.cfg.rope_doc_reset
+            else None
+        )
         for layer in self.layers:
             if self.checkpoint_activations and self.training:
                 x = torch.utils.checkpoint.checkpoint(
-                    layer, x, cos, sin, doc_mask, use_reentrant=False
+                    layer, x, cos, sin, doc_mask, positions, use_reentrant=False
                 )
             else:
-                x = layer(x, cos, sin, doc_mask)
+                x = layer(x, cos, sin, doc_mask, positions)
         return self.norm(x)
 
     def forward(
@@ -248,7 +299,8 @@ class Llama(nn.Module):
         that supports ``ignore_index`` masking and ``z_loss``.
 
         ``doc_mask``: document-masked attention for packed rows, see
-        forward_hidden (global rotary positions)."""
+        forward_hidden (rotary positions global, or per document with
+        ``LlamaConfig.rope_doc_reset``)."""
         if fused is None:
             fused = fused_ce_enabled()
         if not fused and (ignore_index != -100 or z_loss != 0.0):

@@ -1,4 +1,5 @@
-"""CDNA4 fused ops: RMSNorm, RoPE, SwiGLU, fused AdamW (with optional fused
+"""CDNA4 fused ops: RMSNorm, RoPE, the fused QKV split + RoPE (``qkv_rope``,
+with per-token positions for packed rows), SwiGLU, fused AdamW (with optional fused
 global-norm clipping), gradient norm / clip, the fused loss head and the
 fused DiLoCo outer sync (``pseudograd_``, ``diloco_outer_step_``).
 
@@ -133,6 +134,16 @@ class _RopeFn(torch.autograd.Function):
         return hip_ext().rope_apply(dy, cos, sin, True), None, None
 
 
+def _rotate_half(x: torch.Tensor, c: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """The plain-torch rotation of [B, S, H, D] by tables that broadcast
+    against [B, S, H, D/2]; autograd comes through the torch ops."""
+    x1, x2 = x.chunk(2, dim=-1)
+    return torch.cat(
+        [x1 * c.to(x.dtype) - x2 * s.to(x.dtype), x2 * c.to(x.dtype) + x1 * s.to(x.dtype)],
+        dim=-1,
+    )
+
+
 def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     """Apply rotary embedding to [B, S, H, D] (fused on HIP)."""
     if x.is_cuda:
@@ -140,11 +151,76 @@ def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
     S, D = x.shape[1], x.shape[-1]
     c = cos[:S].view(1, S, 1, D // 2)
     s = sin[:S].view(1, S, 1, D // 2)
-    x1, x2 = x.chunk(2, dim=-1)
-    return torch.cat(
-        [x1 * c.to(x.dtype) - x2 * s.to(x.dtype), x2 * c.to(x.dtype) + x1 * s.to(x.dtype)],
-        dim=-1,
-    )
+    return _rotate_half(x, c, s)
+
+
+# ----------------------------------------------------------------- QKV split + RoPE
+
+
+class _QkvRopeFn(torch.autograd.Function):
+    """csrc/kernels/qkv_rope.hip. The rotation needs no activations: only the
+    tables and the positions are saved, so ``qkv`` is free as soon as the
+    projection's own backward no longer needs it."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, n_heads: int, n_kv_heads: int, positions):
+        ctx.save_for_backward(cos, sin, positions)
+        q, k, v = hip_ext().qkv_rope_fwd(qkv, cos, sin, n_heads, n_kv_heads, positions)
+        return q, k, v
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        # an output nobody used arrives as zeros (materialize_grads), so the
+        # kernel always has its three inputs and writes all of dqkv
+        cos, sin, positions = ctx.saved_tensors
+        dqkv = hip_ext().qkv_rope_bwd(dq, dk, dv, cos, sin, positions)
+        # the tables, the head counts and the positions take no gradient
+        return dqkv, None, None, None, None, None
+
+
+def qkv_rope(
+    qkv: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    n_heads: int,
+    n_kv_heads: int,
+    positions: Optional[torch.Tensor] = None,
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Split a fused projection ``qkv`` [B, S, (n_heads + 2 * n_kv_heads) * D]
+    (q heads, then k heads, then v heads) into q [B, S, n_heads, D] and k, v
+    [B, S, n_kv_heads, D] and apply the rotary embedding to q and k.
+
+    ``positions`` (int32 [B, S], e.g. ``DocMask.positions()``): the row of
+    ``cos`` / ``sin`` every token is rotated by; without it token ``s`` reads
+    row ``s``. Values outside the tables give unspecified results.
+
+    On a HIP device one kernel each way (bf16, ``D % 16 == 0``): the forward
+    reads ``qkv`` once and writes three contiguous tensors, the backward
+    writes the whole gradient of ``qkv`` from the three incoming ones. On CPU:
+    slices plus the rotate-half math of :func:`rope`."""
+    if qkv.is_cuda:
+        return _QkvRopeFn.apply(qkv, cos, sin, n_heads, n_kv_heads, positions)
+    B, S, W = qkv.shape
+    D = W // (n_heads + 2 * n_kv_heads)
+    if D * (n_heads + 2 * n_kv_heads) != W:
+        raise ValueError(
+            f"qkv_rope: the last dimension of qkv ({W}) must be divisible by "
+            f"n_heads + 2 * n_kv_heads = {n_heads} + 2 * {n_kv_heads}"
+        )
+    nq, nkv = n_heads * D, n_kv_heads * D
+    q = qkv[..., :nq].view(B, S, n_heads, D)
+    k = qkv[..., nq : nq + nkv].view(B, S, n_kv_heads, D)
+    v = qkv[..., nq + nkv :].view(B, S, n_kv_heads, D)
+    if positions is None:
+        return rope(q, cos, sin), rope(k, cos, sin), v
+    if positions.shape != (B, S):
+        raise ValueError(
+            f"qkv_rope: positions must be [B, S] = {(B, S)}, got {tuple(positions.shape)}"
+        )
+    idx = positions.long()
+    c = cos[idx].view(B, S, 1, D // 2)
+    s = sin[idx].view(B, S, 1, D // 2)
+    return _rotate_half(q, c, s), _rotate_half(k, c, s), v
 
 
 # ----------------------------------------------------------------- SwiGLU

@@ -18,6 +18,8 @@ Packed sequences: ``flash_attention(..., doc_mask=DocMask...)`` keeps every
 token inside its own document (causal within the document). With a mask the
 hand-written forward always runs, whatever TORCHFT_AMD_CUSTOM_FA_FWD says:
 aten's flash forward takes no mask. docs/KERNELS.md, "document mask".
+``DocMask.positions()`` gives the position of every token inside its document,
+for ``ops.qkv_rope`` to restart the rotary positions at document starts.
 """
 
 from __future__ import annotations
@@ -111,6 +113,21 @@ class DocMask:
             rows.append(torch.repeat_interleave(
                 torch.arange(len(row)), torch.tensor(row)))
         return cls.from_doc_ids(torch.stack(rows).to(device))
+
+    def positions(self) -> torch.Tensor:
+        """The position of every token inside its own document, int32
+        ``[B, S]``: ``arange(S) - doc_start``, so positions restart at 0 where
+        a document starts. What ``ops.qkv_rope`` takes to rotate a packed
+        document as it would be rotated alone. Computed on the mask's device
+        without a host sync, once: the result is kept on the instance."""
+        cached = self.__dict__.get("_positions")
+        if cached is None:
+            S = self.doc_start.shape[1]
+            pos = torch.arange(S, device=self.doc_start.device, dtype=torch.int32)
+            cached = (pos - self.doc_start).to(torch.int32).contiguous()
+            # frozen dataclass: the cache is no field and takes no part in ==
+            object.__setattr__(self, "_positions", cached)
+        return cached
 
     def dense(self) -> torch.Tensor:
         """The mask as bool [B, 1, S, S], True = visible. For fallbacks and
