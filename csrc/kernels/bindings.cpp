@@ -317,7 +317,8 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                                     at::Tensor invrms) {
   OpArgs a("rmsnorm_bwd", "x", x);
   const int H = a.dim8("the last dimension of x (H)", a.first.size(-1));
-  TORCH_CHECK(H * (int64_t)sizeof(float) <= tft::kRmsnormBwdMaxLdsBytes,
+  TORCH_CHECK(H * (int64_t)sizeof(float) + tft::kRmsnormBwdStaticLdsBytes <=
+                  tft::kRmsnormBwdMaxLdsBytes,
               "rmsnorm_bwd: the last dimension of x (H) is too large for the LDS dw ",
               "buffer, got ", H);
   const int64_t rows = a.rows();
@@ -326,9 +327,10 @@ std::vector<at::Tensor> rmsnorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
   auto invc = a.flat("invrms", invrms, at::kFloat, rows);
   auto dx = at::empty_like(a.first);
   auto dw = at::zeros({H}, a.first.options().dtype(at::kFloat));
-  tft::launch_rmsnorm_bwd(dyc.data_ptr(), a.first.data_ptr(), wc.data_ptr(),
-                          invc.data_ptr<float>(), dx.data_ptr(), dw.data_ptr<float>(),
-                          rows, H, current_stream());
+  const int status = tft::launch_rmsnorm_bwd(
+      dyc.data_ptr(), a.first.data_ptr(), wc.data_ptr(), invc.data_ptr<float>(),
+      dx.data_ptr(), dw.data_ptr<float>(), rows, H, current_stream());
+  TORCH_CHECK(status == 0, "rmsnorm_bwd: the launch failed with HIP error ", status);
   return {dx, dw};
 }
 

@@ -12,6 +12,7 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdint>
 
 #include "kernels.h"
@@ -29,6 +30,8 @@ __device__ inline float block_reduce_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   __shared__ float wsum[THREADS / 64];
+  static_assert(THREADS != 256 || sizeof(wsum) == kRmsnormBwdStaticLdsBytes,
+                "rmsnorm_bwd's H limit counts this array");
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   if (lane == 0) wsum[wave] = v;
@@ -79,6 +82,7 @@ __global__ void rmsnorm_fwd_kernel(const bf16* __restrict__ x,
 // Grid-strided rows; per-block dw accumulated in LDS (fp32), one atomicAdd
 // sweep per block at the end. dw_out must be fp32 zeros [H].
 // dx = invrms * w * dy - (invrms^3 / H) * x * sum(dy*w*x)
+// LDS: dw[H] (dynamic) + block_reduce_sum's static array.
 template <int THREADS>
 __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
                                    const bf16* __restrict__ x,
@@ -107,7 +111,11 @@ __global__ void rmsnorm_bwd_kernel(const bf16* __restrict__ dy,
       for (int i = 0; i < 8; i++) s += d[i] * g[i] * v[i];
     }
     s = block_reduce_sum<THREADS>(s);
-    const float k = inv * inv * inv * s / H;
+    // inv^3 leaves the fp32 normal range for rows of |x| ~ 2^42 and beyond;
+    // those take inv * s first, which is of the order of H * dy * w at any
+    // scale. Every other row keeps the order, and the bits, it always had.
+    const float inv3 = inv * inv * inv;
+    const float k = inv3 >= FLT_MIN ? inv3 * s / H : inv * s / H * inv * inv;
 
     for (int base = threadIdx.x * 8; base < H; base += THREADS * 8) {
       float d[8], v[8], g[8], o[8];
@@ -283,16 +291,19 @@ void launch_rmsnorm_fwd(const void* x, const void* w, void* y, float* invrms,
                      rows, H, eps);
 }
 
-void launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
-                        const float* invrms, void* dx, float* dw, int64_t rows,
-                        int H, hipStream_t stream) {
-  if (rows == 0) return;
+int launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
+                       const float* invrms, void* dx, float* dw, int64_t rows,
+                       int H, hipStream_t stream) {
+  if (rows == 0) return 0;
   // grid: enough blocks to fill 256 CUs x ~4, capped so atomics stay cheap
   int grid = (int)(rows < 2048 ? rows : 2048);
-  size_t lds = (size_t)H * sizeof(float);  // <= kRmsnormBwdMaxLdsBytes
+  // + kRmsnormBwdStaticLdsBytes <= kRmsnormBwdMaxLdsBytes
+  size_t lds = (size_t)H * sizeof(float);
+  (void)hipGetLastError();  // an earlier call's error is not this launch's
   hipLaunchKernelGGL((rmsnorm_bwd_kernel<256>), dim3(grid), dim3(256), lds, stream,
                      (const bf16*)dy, (const bf16*)x, (const bf16*)w, invrms,
                      (bf16*)dx, dw, rows, H);
+  return (int)hipGetLastError();
 }
 
 // One lane per `per_lane` items, elementwise_grid workgroups of kElemThreads;

@@ -63,10 +63,13 @@ void launch_reduce(const uint8_t* in, uint8_t* out, int world,
 // D % 8 == 0, n % 8 == 0, f % 8 == 0. No rows or no elements: no launch.
 void launch_rmsnorm_fwd(const void* x, const void* w, void* y, float* invrms,
                         int64_t rows, int H, float eps, tft_stream stream);
-// a workgroup keeps its fp32 dw[H] in LDS: H * 4 <= kRmsnormBwdMaxLdsBytes;
-// dw must be zeros
+// a workgroup keeps its fp32 dw[H] in dynamic LDS next to the static LDS of
+// block_reduce_sum<256> (one float per wave; the .hip file asserts the size):
+// H * 4 + kRmsnormBwdStaticLdsBytes <= kRmsnormBwdMaxLdsBytes, so H <= 40952.
+// dw must be zeros. Returns the launch's HIP status, 0 for success.
 constexpr int64_t kRmsnormBwdMaxLdsBytes = 160 * 1024;
-void launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
+constexpr int64_t kRmsnormBwdStaticLdsBytes = 16;
+int launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                         const float* invrms, void* dx, float* dw, int64_t rows,
                         int H, tft_stream stream);
 // The launchers below give every lane `per_lane` items (4 pairs, 8

@@ -8,6 +8,8 @@ refused by name before a launch."""
 import pytest
 import torch
 
+import model_ops_check as mc
+
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
@@ -47,22 +49,25 @@ def _assert_same_bits(got, want):
 # ---------------------------------------------------------------- numerics
 
 
+# Held to fp64 under the derived bounds of tests/model_ops_check.py; the families
+# built to show a wrong kernel are in tests/test_model_ops_numerics_gpu.py.
+
+
 # (1, 8): one vector, 255 idle lanes; 2056 = 256*8 + 8: one lane's second trip
 @pytest.mark.parametrize("rows,H", [(1, 8), (3, 2056)])
 def test_rmsnorm_forward(dev, ext, rows, H):
-    from torchft_amd.ops import rmsnorm_ref
-
     x = _randn(dev, rows, H, seed=1)
     w = _randn(dev, H, seed=2)
     y, invrms = ext.rmsnorm_fwd(x, w, EPS)
     assert invrms.shape == (rows,) and invrms.dtype == torch.float32
-    torch.testing.assert_close(y, rmsnorm_ref(x, w, EPS), rtol=1e-2, atol=1e-2)
+    mc.check_rmsnorm_fwd(f"rmsnorm_fwd ({rows}, {H})", y, invrms, x, w, EPS)
 
 
 def test_rmsnorm_backward_more_rows_than_workgroups(dev, ext):
     """2049 rows on a grid capped at 2048: one workgroup takes two rows and the
     dw atomics see all 2048 workgroups."""
     from torchft_amd.ops import rmsnorm
+    from torchft_amd.ops.model_ops_ref import rmsnorm_bwd_ref64
 
     rows, H = 2049, 8
     x = _randn(dev, rows, H, seed=3).requires_grad_(True)
@@ -70,59 +75,59 @@ def test_rmsnorm_backward_more_rows_than_workgroups(dev, ext):
     dy = _randn(dev, rows, H, seed=5)
     rmsnorm(x, w, EPS).backward(dy)
 
-    xf = x.detach().float().requires_grad_(True)
-    wf = w.detach().float().requires_grad_(True)
-    inv = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + EPS)
-    (xf * inv * wf).backward(dy.float())
-    torch.testing.assert_close(x.grad.float(), xf.grad, rtol=5e-2, atol=5e-2)
-    torch.testing.assert_close(w.grad.float(), wf.grad, rtol=5e-2, atol=5e-1)
-
-    # the binding's fp32 dw against sum_rows dy * x * invrms in fp64, from the
-    # kernel's own invrms. Per column the kernel rounds each product twice
-    # (two fp32 multiplies) and adds the rows one at a time in some order: at
-    # most rows + 1 roundings of partial sums that never exceed sum |term|,
-    # each 2^-24 relative; (rows + 8) * 2^-23 leaves a factor of two.
+    # the binding's bf16 dx under u |ref| + k e mag and its fp32 dw against
+    # sum_rows dy * x * invrms in fp64, from the kernel's own invrms. Per column
+    # the kernel rounds each product twice (two fp32 multiplies) and adds the
+    # rows one at a time in some order: at most rows + 1 roundings of partial
+    # sums that never exceed sum |term|, each 2^-24 relative; (rows + 8) * 2^-23
+    # leaves a factor of two.
     xd, wd = x.detach(), w.detach()
     _, invrms = ext.rmsnorm_fwd(xd, wd, EPS)
-    _, dw = ext.rmsnorm_bwd(dy, xd, wd, invrms)
+    dx, dw = ext.rmsnorm_bwd(dy, xd, wd, invrms)
     assert dw.shape == (H,) and dw.dtype == torch.float32
-    terms = dy.double() * xd.double() * invrms.double()[:, None]
-    err = (dw.double() - terms.sum(0)).abs()
-    bound = (rows + 8) * 2.0 ** -23 * terms.abs().sum(0)
-    print("rmsnorm dw err / bound per column:", (err / bound).tolist())
-    assert torch.all(err <= bound)
+    mc.check_rmsnorm_bwd("rmsnorm_bwd (2049, 8)", dx, dw, dy, xd, wd, invrms)
+    # autograd's dx is the binding's; its dw is one more rounding, to bf16
+    _assert_same_bits(x.grad, dx)
+    r = rmsnorm_bwd_ref64(dy.cpu(), xd.cpu(), wd.cpu(), invrms.cpu())
+    bound = (rows + 8) * 2.0 ** -23 * r.dw_abs
+    assert w.grad.dtype == BF16
+    err = (w.grad.cpu().double() - r.dw).abs()
+    assert torch.all(err <= mc.U * r.dw.abs() + (1 + mc.U) * bound)
 
 
 # (1, 3, 1, 8): halfD = 4, one thread per row; (2, 5, 3, 16) with 9 table rows:
 # the table is longer than S and a row takes two threads
 @pytest.mark.parametrize("shape,table_rows", [((1, 3, 1, 8), 3), ((2, 5, 3, 16), 9)])
 def test_rope_forward_backward(dev, ext, shape, table_rows):
-    from torchft_amd.ops import rope, rope_ref, rope_tables
+    from torchft_amd.ops import rope, rope_tables
+    from torchft_amd.ops.model_ops_ref import rotate_ref64
 
     S, D = shape[1], shape[3]
     cos, sin = rope_tables(table_rows, D, device=dev)
     x = _randn(dev, *shape, seed=6).requires_grad_(True)
     out = rope(x, cos, sin)
-    torch.testing.assert_close(out, rope_ref(x.detach(), cos, sin), rtol=2e-2, atol=2e-2)
+    mc.check_rope(f"rope {shape}", out.detach(), x.detach(), cos, sin, False)
 
     dy = _randn(dev, *shape, seed=7)
     out.backward(dy)
-    xf = x.detach().float().requires_grad_(True)
-    c = cos[:S].view(1, S, 1, D // 2)
-    s = sin[:S].view(1, S, 1, D // 2)
-    x1, x2 = xf.chunk(2, dim=-1)
-    torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).backward(dy.float())
-    torch.testing.assert_close(x.grad.float(), xf.grad, rtol=2e-2, atol=2e-2)
+    mc.check_rope(f"rope {shape} grad", x.grad, dy, cos, sin, True)
 
-    # the rotation's transpose undoes it
+    # the rotation's transpose undoes it: back = R^T out carries its own
+    # roundings, (u + 3e) mag, the forward's, (u + 3e) mag, taken through
+    # |R^T|, and c^2 + s^2 = 1 only as far as the tables go: cos and sin within
+    # 2 ulp = 4e each, doubled in the squares, 8e |x|
     back = ext.rope_apply(out.detach(), cos, sin, True)
-    torch.testing.assert_close(back, x.detach(), rtol=2e-2, atol=2e-2)
-
-
-def _check_swiglu(y, grads, ref, ref_grads):
-    torch.testing.assert_close(y.float(), ref, rtol=2e-2, atol=2e-2)
-    for g, r in zip(grads, ref_grads):
-        torch.testing.assert_close(g.float(), r, rtol=3e-2, atol=3e-2)
+    mc.check_rope(f"rope {shape} transpose", back, out.detach(), cos, sin, True)
+    xc, oc = x.detach().cpu(), out.detach().cpu()
+    _, mag_f = rotate_ref64(xc, cos.cpu(), sin.cpu(), False)
+    _, mag_b = rotate_ref64(oc, cos.cpu(), sin.cpu(), True)
+    c = cos[:S].cpu().double().abs().view(1, S, 1, D // 2)
+    s = sin[:S].cpu().double().abs().view(1, S, 1, D // 2)
+    f1, f2 = mag_f.chunk(2, dim=-1)
+    through = torch.cat([c * f1 + s * f2, c * f2 + s * f1], dim=-1)
+    x1, x2 = xc.double().abs().chunk(2, dim=-1)
+    bound = (mc.U + 3 * mc.E) * (mag_b + through) + 8 * mc.E * torch.cat([x1 + x2, x1 + x2], -1)
+    assert torch.all((back.cpu().double() - xc.double()).abs() <= bound)
 
 
 @pytest.mark.parametrize("n", [8, 2056])
@@ -134,12 +139,8 @@ def test_swiglu_plain(dev, n):
     dy = _randn(dev, n, seed=10)
     y = swiglu(a, b)
     y.backward(dy)
-
-    af = a.detach().float().requires_grad_(True)
-    bf = b.detach().float().requires_grad_(True)
-    ref = torch.nn.functional.silu(af) * bf
-    ref.backward(dy.float())
-    _check_swiglu(y, [a.grad, b.grad], ref.detach(), [af.grad, bf.grad])
+    mc.check_swiglu_fwd(f"swiglu n={n}", y.detach(), a.detach(), b.detach())
+    mc.check_swiglu_bwd(f"swiglu n={n}", a.grad, b.grad, dy, a.detach(), b.detach())
 
 
 # (3, 264): a row boundary inside a workgroup, 2f = 528 not a power of two
@@ -152,11 +153,10 @@ def test_swiglu_packed(dev, rows, f):
     y = swiglu_glu(gu)
     assert y.shape == (rows, f)
     y.backward(dy)
-
-    guf = gu.detach().float().requires_grad_(True)
-    ref = torch.nn.functional.silu(guf[..., :f]) * guf[..., f:]
-    ref.backward(dy.float())
-    _check_swiglu(y, [gu.grad], ref.detach(), [guf.grad])
+    g = gu.detach()
+    mc.check_swiglu_fwd(f"swiglu_glu ({rows}, {f})", y.detach(), g[:, :f].contiguous(),
+                        g[:, f:].contiguous())
+    mc.check_swiglu_glu_bwd(f"swiglu_glu ({rows}, {f})", gu.grad, dy, g)
 
 
 # ---------------------------------------------------------------- the argument rule
@@ -275,6 +275,14 @@ def test_zero_sized_inputs_launch_nothing(dev, ext):
     assert (torch.ones(4, device=dev) + 1).sum().item() == 8.0
 
 
+H_MAX = 40952  # the largest H rmsnorm_bwd accepts (kernels.h)
+
+
+def _rmsnorm_bwd_args(dev, H):
+    z = torch.zeros(2, H, device=dev, dtype=BF16)
+    return dict(dy=z, x=z, w=z[0], invrms=torch.ones(2, device=dev))
+
+
 def _refusals(dev):
     """(binding, argument named in the message, arguments) of every refusal."""
     def args(name, **changed):
@@ -293,11 +301,17 @@ def _refusals(dev):
         ("rmsnorm_fwd", "x", dict(x=x12, w=_randn(dev, 12, seed=45))),
         ("swiglu_glu_fwd", "gu", dict(gu=_randn(dev, 4, 17, seed=46))),
         ("rmsnorm_fwd", "x", args("rmsnorm_fwd", x=torch.ones(2, 16, device=dev))),
+        # dw[H] and the 16 static bytes of the block reduction fill the LDS at H_MAX
+        # the first H past the limit, which is 40960 and named in the message,
+        # and one further out
+        ("rmsnorm_bwd", "x", _rmsnorm_bwd_args(dev, H_MAX + 16)),
+        ("rmsnorm_bwd", "40960", _rmsnorm_bwd_args(dev, H_MAX + 8)),
     ]
 
 
 REFUSAL_IDS = ["cpu-cos_tab", "sin_tab-one-column-short", "fp16-dy", "invrms-rows-minus-1",
-               "w-H-plus-8", "b-8-short", "dy-full-2f-width", "H-12", "odd-gu", "fp32-x"]
+               "w-H-plus-8", "b-8-short", "dy-full-2f-width", "H-12", "odd-gu", "fp32-x",
+               "H_MAX-plus-16", "H-40960"]
 
 
 @pytest.mark.parametrize("case", range(len(REFUSAL_IDS)), ids=REFUSAL_IDS)
