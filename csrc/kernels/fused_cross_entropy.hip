@@ -17,7 +17,10 @@
 // has one finite logit. Rows with t == ignore_index give loss 0 and a zero
 // gradient row. A target outside [0, V) that is not ignore_index gives a NaN
 // loss and a NaN gradient row; no address is ever formed from it (the
-// one-hot is a column compare and the x[t] read is guarded).
+// one-hot is a column compare and the x[t] read is guarded). A NaN or +inf
+// logit gives a non-finite loss and no finite gradient element (NaN for +inf,
+// where the definition has a +inf loss: inf - inf below); a target on a -inf
+// logit gives a +inf loss and a finite gradient row.
 //
 // Any V >= 1 and any 2-byte-aligned row base: each row is split into a
 // scalar head (up to the first 16-B boundary), whole 16-B bf16x8 vectors,
@@ -127,6 +130,15 @@ cross_entropy_kernel(bf16* __restrict__ logits,
   if (tid < sp.nscalar) {
     const float v = __bfloat162float(xr[ce_scalar_col(sp, tid)]);
     ce_combine(m, s, v, 1.f);
+    // fmaxf drops a NaN, and a lane that has seen no finite logit (none has a
+    // vector of its own when V is small) would stay at (-inf, 0), which every
+    // later combine with another empty lane resets to s = 0: the row's loss
+    // would come out finite. A finite m keeps the NaN in s through them all;
+    // its value is of no account, every output of the row is NaN.
+    if (v != v) {
+      m = 0.f;
+      s = v;
+    }
   }
 
 #pragma unroll

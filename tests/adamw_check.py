@@ -50,6 +50,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
+from grad_norm_check import coef_from_sumsq32
 from torchft_amd.ops.adamw_ref import AdamWRef
 
 U32 = 2.0 ** -24
@@ -208,4 +209,4 @@ def clip_coef32(grads: List[torch.Tensor], max_norm: float) -> torch.Tensor:
     sumsq = torch.zeros((), dtype=torch.float32)
     for g in grads:
         sumsq = sumsq + g.float().pow(2).sum()
-    return torch.clamp(_t32(max_norm) / (sumsq.sqrt() + _t32(1e-6)), max=1.0)
+    return coef_from_sumsq32(sumsq, max_norm)

@@ -15,6 +15,8 @@ import math
 import pytest
 import torch
 
+from grad_norm_check import depth as _depth
+
 pytestmark = pytest.mark.gpu
 
 HP = dict(lr=1e-2, betas=(0.9, 0.95), weight_decay=0.01, eps=1e-8)
@@ -25,12 +27,6 @@ BF16_ULP = dict(rtol=2**-7, atol=0)
 @pytest.fixture
 def dev():
     return torch.device("cuda:0")
-
-
-def _depth(numels, max_blocks=2048):
-    blocks = sum((n + 2047) // 2048 for n in numels)
-    grid = min(blocks, max_blocks)
-    return 8 * math.ceil(blocks / grid) + 6 + 3
 
 
 def _ref_norm(tensors):

@@ -335,6 +335,12 @@ def grad_norm(tensors_or_params, *, norm_reduce=None, max_blocks: int = 2048) ->
     on the reduction grid). ``norm_reduce``, if given, is called with the
     1-element fp32 sum of squares before the square root — sharded callers
     all-reduce (SUM) it there. On CPU: plain torch.
+
+    The sum of squares is an fp32 number: finite gradients whose squares add
+    up past 2**128 (``|g| >= 2**64`` in bf16 or fp32) give an ``inf`` norm.
+    ``clip_grad_norm_`` then leaves the gradients untouched and
+    ``FusedAdamW(max_grad_norm=...)`` skips the step and counts it, as for a
+    non-finite gradient (docs/KERNELS.md, "Overflow rule").
     """
     grads = _as_grads(tensors_or_params)
     if not grads:

@@ -16,7 +16,11 @@ Per row, in fp32, with ``lse = logsumexp(x)``::
 
 A row whose target equals ``ignore_index`` has loss 0 and a zero gradient.
 A target outside ``[0, V)`` that is not ``ignore_index`` is an error made
-loud: that row's loss and gradient are NaN.
+loud: that row's loss and gradient are NaN. A row with a NaN or ``+inf`` logit,
+or with no finite logit at all, has a non-finite loss and no finite gradient
+element (the kernel gives NaN for a ``+inf`` logit where the definition gives
+a ``+inf`` loss; docs/KERNELS.md, "Numerics"). ``-inf`` logits are fine; a
+target on one gives a ``+inf`` loss and a finite gradient.
 """
 
 from __future__ import annotations
@@ -86,6 +90,10 @@ def fused_cross_entropy_(
         if not isinstance(grad_scale, torch.Tensor):
             grad_scale = torch.full(
                 (1,), float(grad_scale), dtype=torch.float32, device=logits.device
+            )
+        if grad_scale.numel() != 1:
+            raise ValueError(
+                f"grad_scale must have one element, got {grad_scale.numel()}"
             )
         return hip_ext().cross_entropy_fwd_bwd(
             logits, targets, int(ignore_index), float(z_loss),
