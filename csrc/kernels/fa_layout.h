@@ -1,10 +1,10 @@
 // Address math of the flash-attention kernels (flash_attn_fwd.hip,
-// flash_attn_bwd.hip): the sizes, the subtiled LDS tile image, the
-// thread -> chunk staging map, the tr_b16 read offsets, the pa/pb swizzle and
-// the tile bounds of the document mask. Plain constexpr C++, callable from
-// host and device; the device-only pieces built on it are in fa_tile.h.
-// csrc/kernels/tests/fa_layout_test.cpp and fa_doc_bounds_test.cpp check
-// every function here on the host.
+// flash_attn_bwd.hip): the sizes, the workgroup order, the subtiled LDS tile
+// image, the thread -> chunk staging map, the tr_b16 read offsets, the pa/pb
+// swizzle and the tile bounds of the document mask. Plain constexpr C++,
+// callable from host and device; the device-only pieces built on it are in
+// fa_tile.h. csrc/kernels/tests/fa_layout_test.cpp, fa_wg_order_test.cpp and
+// fa_doc_bounds_test.cpp check every function here on the host.
 #pragma once
 
 #include "kernels.h"
@@ -18,6 +18,36 @@ constexpr int kFaBlk = 32;       // rows of one wave's block (one MFMA tile)
 static_assert(kFaThreads == kFaWaves * 64, "wave64");
 // the attention launches put batch * heads in gridDim.y
 constexpr int kFaMaxGridY = 65535;
+
+// ---- workgroup order ----------------------------------------------------------
+// The launches are (nx = blocks of 256 rows, ny = batch * heads). Under a
+// causal mask the tiles a workgroup streams grow or shrink with its block x,
+// and only one workgroup fits a CU, so the order in which blocks start
+// decides how long the tail of a launch is. fa_wg_order maps the launch's
+// block id to the (x, y) the kernel works on: with n = bx + nx * by, all ny
+// (batch, head) pairs of the heaviest x come first and all pairs of the
+// lightest x last. kFaHeavyLowX: x = 0 is the heaviest (dkdv, whose block x
+// streams the query tiles at and after its keys); kFaHeavyHighX: x = nx - 1 is
+// (dq and the forward, whose block x streams the keys at and before its rows).
+// Without the causal flag the workgroups are equal and the map is the
+// identity. It is a bijection of the grid either way
+// (csrc/kernels/tests/fa_wg_order_test.cpp), every (x, y) does the work it
+// always did, and results do not depend on the order blocks are dealt in:
+// this is for speed only (docs/KERNELS.md, "Workgroup order").
+// 32 bits hold n: q alone has nx * ny * 256 rows of 256 bytes, so n < 2^32
+// wherever q fits in 2^48 bytes; the largest grid the bindings could admit
+// (ny = kFaMaxGridY, S = 2^24) gives 65536 * 65535 < 2^32.
+enum FaHeavy { kFaHeavyLowX, kFaHeavyHighX };
+struct FaWg {
+  int x, y;
+};
+TFT_HD constexpr FaWg fa_wg_order(unsigned bx, unsigned by, unsigned nx, unsigned ny,
+                                  bool causal, FaHeavy heavy) {
+  if (!causal) return {(int)bx, (int)by};
+  const unsigned n = bx + nx * by;
+  const unsigned rank = n / ny;
+  return {(int)(heavy == kFaHeavyLowX ? rank : nx - 1 - rank), (int)(n % ny)};
+}
 
 // One ROWS x 128 bf16 tile in LDS = 8 subtiles of [ROWS rows][16 cols], each
 // row-major and element-contiguous (tr_b16 needs its [4][16] blocks

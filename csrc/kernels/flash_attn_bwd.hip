@@ -81,16 +81,19 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
   static_assert(sizeof...(DocP) == (DOC ? 2 : 0), "DOC takes doc_start, doc_end");
   __shared__ SmemFA sm;
   const int G = Hq / Hkv;
-  const int b = blockIdx.y / Hkv;
-  const int hkv = blockIdx.y % Hkv;
+  // causal: block 0 streams the most query tiles; all heads of it start first
+  const FaWg wg =
+      fa_wg_order(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, causal, kFaHeavyLowX);
+  const int b = wg.y / Hkv;
+  const int hkv = wg.y % Hkv;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
   const int l31 = lane & 31;
-  const int jb = blockIdx.x * kFaWaves + wave;
+  const int jb = wg.x * kFaWaves + wave;
   const bool active = jb * kFaBlk < S;
   const int nQ = S / kFaBlk;
-  const int i_min = causal ? blockIdx.x * kFaWaves : 0;
+  const int i_min = causal ? wg.x * kFaWaves : 0;
   // DOC: the query tiles end where the document of the workgroup's last key
   // ends; a wave stops computing at doc_end of its own last key (de_w)
   int i_hi = nQ, de_w = 0;
@@ -98,7 +101,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
   if constexpr (DOC) {
     ds_base = doc_ptr<0>(docp...) + (int64_t)b * S;
     const int* doc_end = doc_ptr<1>(docp...) + (int64_t)b * S;
-    const int wg_last = min((int)(blockIdx.x + 1) * kFaWaves * kFaBlk, S) - 1;
+    const int wg_last = min((wg.x + 1) * kFaWaves * kFaBlk, S) - 1;
     i_hi = doc_last_qtile(doc_end[wg_last], i_min, nQ);
     if (active) {
       de_w = __builtin_amdgcn_readfirstlane(doc_end[jb * kFaBlk + kFaBlk - 1]);
@@ -325,15 +328,18 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
   static_assert(sizeof...(DocP) == (DOC ? 1 : 0), "DOC takes doc_start");
   __shared__ std::conditional_t<DOC, SmemDqDoc, SmemDq> sm;
   const int G = Hq / Hkv;
-  const int b = blockIdx.y / Hq;
-  const int hq = blockIdx.y % Hq;
+  // causal: the last q block streams the most key tiles; all heads of it
+  // start first
+  const FaWg wg =
+      fa_wg_order(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, causal, kFaHeavyHighX);
+  const int b = wg.y / Hq;
+  const int hq = wg.y % Hq;
   const int hkv = hq / G;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
   const int l31 = lane & 31;
-  // causal: the last q block streams the most key tiles — dispatch it first
-  const int bx = causal ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
+  const int bx = wg.x;
   const int ib = bx * kFaWaves + wave;
   const bool active = ib * kFaBlk < S;
   const int nK64 = (S + 63) / 64;

@@ -107,15 +107,19 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
   static_assert(sizeof...(DocP) == (DOC ? 1 : 0), "DOC takes doc_start");
   __shared__ SmemFwd sm;
   const int G = Hq / Hkv;
-  const int b = blockIdx.y / Hq;
-  const int hq = blockIdx.y % Hq;
+  // causal: the last q block streams the most key tiles; all heads of it
+  // start first
+  const FaWg wg =
+      fa_wg_order(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, causal, kFaHeavyHighX);
+  const int b = wg.y / Hq;
+  const int hq = wg.y % Hq;
   const int hkv = hq / G;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
   const int l31 = lane & 31;
 
-  const int Q0 = blockIdx.x * (kFaWaves * kFaBlk);
+  const int Q0 = wg.x * (kFaWaves * kFaBlk);
   const int my_q0 = Q0 + wave * kFaBlk;       // this wave's 32 q rows
   const int q_glob = my_q0 + l31;               // this lane's q row
   const bool active = my_q0 < S;

@@ -19,7 +19,9 @@ events, builds interleaved inside every round (median [min-max] over rounds).
 --check compares every build's dq/dk/dv bit for bit against the baseline at
 (B=1, Hq=8, Hkv=2, S=1024), causal and full, packed and [B,S,H,D] layouts,
 and at the timed shape. --drive N only launches build 0 N times (a profiler
-target). Run on a GPU host."""
+target). --full times or drives the non-causal launch, whose workgroups are
+all equal: causal / full against the tile ratio says how well the causal
+launch is balanced (docs/KERNELS.md, "Workgroup order"). Run on a GPU host."""
 import argparse
 import ctypes
 import os
@@ -105,7 +107,10 @@ def check(builds, shapes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("builds", nargs="+", help="name=path/to/lib.so")
-    ap.add_argument("--shape", default="4,32,8,8192", help="B,Hq,Hkv,S (causal)")
+    ap.add_argument("--shape", default="4,32,8,8192", help="B,Hq,Hkv,S")
+    ap.add_argument("--full", action="store_true", help="non-causal (default: causal)")
+    ap.add_argument("--bshd", action="store_true",
+                    help="[B,S,H,D] storage, the model's layout (default: packed)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--check", action="store_true")
@@ -114,7 +119,7 @@ def main():
     builds = [Build(s) for s in a.builds]
     shape = tuple(int(x) for x in a.shape.split(","))
 
-    p = problem(*shape, True, False)
+    p = problem(*shape, not a.full, a.bshd)
     out = grads(p)
     if a.drive:
         for _ in range(a.drive):
@@ -145,7 +150,8 @@ def main():
             f"{n} {t[-1]:.3f}" for n, t in times.items()), flush=True)
     for n, t in times.items():
         print(f"{n}: dkdv+dq {statistics.median(t):.3f} ms "
-              f"[{min(t):.3f}-{max(t):.3f}] over {len(t)} rounds, shape {shape}")
+              f"[{min(t):.3f}-{max(t):.3f}] over {len(t)} rounds, shape {shape} "
+              f"{'full' if a.full else 'causal'} {'bshd' if a.bshd else 'packed'}")
     return 0 if ok else 1
 
 
