@@ -29,14 +29,26 @@ struct PackGeom {
   int64_t slice_bytes = 0;
 };
 
-PackGeom pack_geometry(const TensorList& tensors, int64_t world, const char* what) {
+int64_t blocks_of(const at::Tensor& t) {
+  return (t.numel() + tft::kMtBlock - 1) / tft::kMtBlock;
+}
+
+// the pack of total_blocks blocks split over `world` slices
+PackGeom pack_geometry(int64_t total_blocks, int64_t world, const char* what) {
   TORCH_CHECK(world >= 1, what, ": world must be >= 1, got ", world);
   PackGeom g;
-  for (auto& t : tensors) g.total_blocks += (t.numel() + tft::kMtBlock - 1) / tft::kMtBlock;
+  g.total_blocks = total_blocks;
   g.padded_blocks = ((g.total_blocks + world - 1) / world) * world;
   g.blocks_per_rank = g.padded_blocks / world;
   g.slice_bytes = g.blocks_per_rank * (4 + tft::kMtBlock);
   return g;
+}
+
+// the pack whose tensor list is `tensors`
+PackGeom pack_geometry(const TensorList& tensors, int64_t world, const char* what) {
+  int64_t total_blocks = 0;
+  for (auto& t : tensors) total_blocks += blocks_of(t);
+  return pack_geometry(total_blocks, world, what);
 }
 
 // dtype_code of kernels.h, -1 for a dtype the multi-tensor kernels do not take
@@ -49,11 +61,20 @@ int dtype_code(at::ScalarType st) {
 
 // One pointer column of a table to be: a tensor list and the dtype every
 // entry must have. `one_element` columns (device step counts) hold 1-element
-// tensors instead of tensors of the row's size.
+// tensors instead of tensors of the row's size. `name`, where given, is the
+// binding's argument and goes into every refusal. A column with `values` set
+// holds those numbers, one per row, instead of addresses (and has no list);
+// column 0 is always a tensor list.
 struct Column {
   const TensorList* list;
   at::ScalarType dtype;
   bool one_element = false;
+  const char* name = nullptr;
+  const std::vector<int64_t>* values = nullptr;
+
+  int64_t size() const { return (int64_t)(values ? values->size() : list->size()); }
+  // " of <name>" for a message
+  std::string of() const { return name ? std::string(" of ") + name : std::string(); }
 };
 
 // Every multi-tensor table of one binding call (kernels.h, MultiTensorTable):
@@ -80,24 +101,30 @@ class TableSet {
     TORCH_CHECK(first >= 0 && count >= 0 && first + count <= len, what_,
                 ": rows out of range");
     for (auto& c : cols)
-      TORCH_CHECK((int64_t)c.list->size() == len, what_, ": list lengths differ");
+      TORCH_CHECK(c.size() == len, what_, ": list lengths differ", c.of());
     for (int64_t i = first; i < first + count; i++) {
       const int64_t ne = (*cols[0].list)[i].numel();
       for (auto& c : cols) {
+        if (c.values) continue;
         const at::Tensor& t = (*c.list)[i];
         TORCH_CHECK(t.is_cuda() && t.device() == dev_, what_,
-                    ": all tensors must be on one device");
+                    ": all tensors must be on one device (tensor ", i, c.of(), ")");
         TORCH_CHECK(t.scalar_type() == c.dtype, what_, ": mixed dtypes (expected ",
-                    c.dtype, ", got ", t.scalar_type(), " at tensor ", i, ")");
-        TORCH_CHECK(t.is_contiguous(), what_, ": tensors must be contiguous");
+                    c.dtype, ", got ", t.scalar_type(), " at tensor ", i, c.of(), ")");
+        TORCH_CHECK(t.is_contiguous(), what_, ": tensors must be contiguous (tensor ", i,
+                    c.of(), ")");
         TORCH_CHECK(t.numel() == (c.one_element ? 1 : ne), what_,
-                    ": size mismatch at tensor ", i);
+                    ": size mismatch at tensor ", i, c.of());
       }
       if (ne == 0) continue;
       for (auto& c : cols) {
+        if (c.values) {
+          st.addrs.push_back((*c.values)[i]);
+          continue;
+        }
         const int64_t addr = (int64_t)(*c.list)[i].data_ptr();
         TORCH_CHECK(!need_16b_alignment_ || (addr & 15) == 0, what_, ": tensor ", i,
-                    " does not start on a 16-byte boundary");
+                    c.of(), " does not start on a 16-byte boundary");
         st.addrs.push_back(addr);
       }
       st.numels.push_back(ne);
@@ -745,6 +772,68 @@ void diloco_outer_step(const std::vector<at::Tensor>& snapshots,
                         nesterov, (float)alpha, current_stream());
 }
 
+// The quantized sync: pack = the fp8 wire pack (fp8_quantize's layout, the
+// minuends as its tensor list) of minuends[i] - subtrahends[i], the difference
+// taken in fp32 and never stored. Every byte of the pack's world slices is
+// written; one launch.
+void diloco_pseudograd_fp8(const std::vector<at::Tensor>& minuends,
+                           const std::vector<at::Tensor>& subtrahends, at::Tensor pack,
+                           int64_t world) {
+  const char* what = "diloco_pseudograd_fp8";
+  const int code = first_dtype_code(minuends, what);
+  const auto st = minuends[0].scalar_type();
+  TORCH_CHECK(minuends[0].is_cuda(), what, ": minuends must be device tensors");
+  const auto g = pack_geometry(minuends, world, what);
+  check_pack(pack, minuends, g, world, what);
+  TableSet tables(minuends[0], what, /*need_16b_alignment=*/true);
+  const int h = tables.add({{&minuends, st, false, "minuends"},
+                            {&subtrahends, st, false, "subtrahends"}});
+  tables.upload();
+  tft::launch_pseudograd_fp8(code, tables.table(h), g.padded_blocks, g.blocks_per_rank,
+                             g.slice_bytes, pack.data_ptr<uint8_t>(), current_stream());
+}
+
+// diloco_outer_step for one param group whose pseudo-gradients are blocks of a
+// reduced pack of pack_total_blocks blocks over `world` slices: tensor i owns
+// the pack blocks from first_blocks[i] on. d = code * (scale * inv_div).
+void diloco_outer_step_fp8(const std::vector<at::Tensor>& snapshots,
+                           const std::vector<at::Tensor>& params, at::Tensor pack,
+                           const std::vector<int64_t>& first_blocks,
+                           int64_t pack_total_blocks, int64_t world,
+                           const std::vector<at::Tensor>& momentum_bufs, double lr,
+                           double momentum, bool nesterov, double alpha, double inv_div) {
+  const char* what = "diloco_outer_step_fp8";
+  const bool has_m = momentum != 0.0;
+  TORCH_CHECK(has_m == !momentum_bufs.empty(), what,
+              ": momentum_bufs are needed exactly when momentum != 0");
+  TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, what, ": alpha must be in [0, 1], got ", alpha);
+  const int code = first_dtype_code(snapshots, what);
+  const auto st = snapshots[0].scalar_type();
+  TORCH_CHECK(snapshots[0].is_cuda(), what, ": snapshots must be device tensors");
+  TORCH_CHECK(pack_total_blocks >= 0, what, ": pack_total_blocks must be >= 0, got ",
+              pack_total_blocks);
+  const auto g = pack_geometry(pack_total_blocks, world, what);
+  check_pack(pack, snapshots, g, world, what);
+  TORCH_CHECK(first_blocks.size() == snapshots.size(), what,
+              ": first_blocks needs one entry per tensor, got ", first_blocks.size(),
+              " for ", snapshots.size());
+  for (size_t i = 0; i < snapshots.size(); i++)
+    TORCH_CHECK(first_blocks[i] >= 0 &&
+                    first_blocks[i] <= pack_total_blocks - blocks_of(snapshots[i]),
+                what, ": first_blocks[", i, "] = ", first_blocks[i], " puts a tensor of ",
+                blocks_of(snapshots[i]), " blocks outside the pack's ", pack_total_blocks);
+  std::vector<Column> cols = {{&snapshots, st, false, "snapshots"},
+                              {&params, st, false, "params"},
+                              {nullptr, at::kLong, false, "first_blocks", &first_blocks}};
+  if (has_m) cols.push_back({&momentum_bufs, st, false, "momentum_bufs"});
+  TableSet tables(snapshots[0], what);
+  const int h = tables.add(cols);
+  tables.upload();
+  tft::launch_outer_sgd_fp8(code, has_m, tables.table(h), pack.data_ptr<uint8_t>(),
+                            g.blocks_per_rank, g.slice_bytes, (float)inv_div, (float)lr,
+                            (float)momentum, nesterov, (float)alpha, current_stream());
+}
+
 // ---- flash attention ----------------------------------------------------------
 
 namespace {
@@ -1009,6 +1098,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "multi-tensor outs[i] = minuends[i] - subtrahends[i]");
   m.def("diloco_outer_step", &diloco_outer_step,
         "fused DiLoCo outer SGD step, re-snapshot and local-progress lerp");
+  m.def("diloco_pseudograd_fp8", &diloco_pseudograd_fp8,
+        "fp8 wire pack of minuends[i] - subtrahends[i], the difference kept in fp32");
+  m.def("diloco_outer_step_fp8", &diloco_outer_step_fp8,
+        "diloco_outer_step with the pseudo-gradients decoded from a reduced fp8 pack");
   m.def("fa_fwd", &fa_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
         py::arg("causal"), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(),

@@ -146,6 +146,21 @@ void launch_pseudograd(int dtype_code, MultiTensorTable tb, tft_stream stream);
 void launch_outer_sgd(int dtype_code, bool has_momentum, MultiTensorTable tb,
                       float lr, float mu, bool nesterov, float alpha,
                       tft_stream stream);
+// The same two ends around the fp8 wire pack of fp8_quant.hip (geometry as for
+// launch_quantize_dtype), so the pseudo-gradient is never stored in T.
+// cols 0..1 = a, b, every one 16 B-aligned: pack = quantize(float(a) - float(b));
+// the grid is padded_blocks workgroups and every byte of the pack is written
+void launch_pseudograd_fp8(int dtype_code, MultiTensorTable tb, int64_t padded_blocks,
+                           int64_t blocks_per_rank, int64_t slice_bytes, uint8_t* pack,
+                           tft_stream stream);
+// cols 0..2 = g, l and (a number, not an address) the tensor's first block in
+// the pack; col 3 = m when has_momentum. launch_outer_sgd with
+// d = code * (scale * inv_div) read from the pack; every tensor's blocks must
+// lie inside the pack (the binding checks)
+void launch_outer_sgd_fp8(int dtype_code, bool has_momentum, MultiTensorTable tb,
+                          const uint8_t* pack, int64_t blocks_per_rank,
+                          int64_t slice_bytes, float inv_div, float lr, float mu,
+                          bool nesterov, float alpha, tft_stream stream);
 
 // flash_attn_fwd.hip --------------------------------------------------------
 // q / k / v / out: bf16, logical [B,H,S,128]; bshd = the storage is

@@ -27,6 +27,8 @@ ap.add_argument("--size", choices=["8b", "1b"], default="8b")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=3)
 ap.add_argument("--alpha", type=float, default=0.25)
+ap.add_argument("--quantized", action="store_true",
+                help="time the fp8-quantized sync both ways (Q0 / Q1) instead of A / B")
 args = ap.parse_args()
 
 assert torch.cuda.is_available(), "bench_diloco_sync.py measures on a HIP device only"
@@ -127,6 +129,58 @@ def timed(fn, iters):
 
 VARIANTS = [("A_unfused_sequence", variant_a), ("B_fused_sync", variant_b),
             ("pseudograd_kernel", pseudograd_only), ("outer_step_kernel", outer_step_only)]
+
+# --quantized: the device work around the fp8 allreduce (world 1, one
+# participant, the collective itself left out), per bucket of the same plan
+#   Q0  zeroed buckets, pseudograd_, fp8 quantize, fp8 dequantize, the
+#       manager's `/= num_participants`, diloco_outer_step_
+#   Q1  fused_fp8_pack=True: pseudograd_fp8_ into a fresh pack, then
+#       diloco_outer_step_fp8_ from it
+if args.quantized:
+    from torchft_amd import quantization as Q
+
+    datas = [p.data for p in params]
+    bounds, start = [], 0
+    for slots in plan.buckets:
+        bounds.append((start, start + len(slots)))
+        start += len(slots)
+    firsts = []
+    for lo, hi in bounds:
+        blocks = [(p.numel() + Q.QBLOCK - 1) // Q.QBLOCK for p in datas[lo:hi]]
+        firsts.append(([sum(blocks[:i]) for i in range(len(blocks))], sum(blocks)))
+
+    def variant_q0():
+        buckets = [plan.allocate(slots) for slots in plan.buckets]
+        views = [v for _, vs in buckets for v in vs]
+        ops.pseudograd_(views, snap_b, datas)
+        for flat, _ in buckets:
+            pack = Q.allocate_pack([flat], 1)
+            Q.quantize_pack([flat], pack, 1)
+            Q.dequantize_pack([flat], pack, 1)
+            flat /= 1
+        fused_step(views)
+
+    def q1_prepare():
+        packs = []
+        for lo, hi in bounds:
+            pack = Q.allocate_pack(datas[lo:hi], 1)
+            ops.pseudograd_fp8_(pack, snap_b[lo:hi], datas[lo:hi], 1)
+            packs.append(pack)
+        return packs
+
+    def q1_step(packs):
+        for (lo, hi), (first, total), pack in zip(bounds, firsts, packs):
+            ops.diloco_outer_step_fp8_(snap_b[lo:hi], datas[lo:hi], pack, first, total, 1,
+                                       mom_b[lo:hi], lr=LR, momentum=MU, nesterov=True,
+                                       alpha=ALPHA, num_participants=1)
+
+    kernel_packs = q1_prepare()
+    VARIANTS = VARIANTS[2:] + [
+        ("Q0_quantized_fused_sequence", variant_q0),
+        ("Q1_fused_fp8_pack", lambda: q1_step(q1_prepare())),
+        ("pseudograd_fp8_kernel", q1_prepare),
+        ("outer_step_fp8_kernel", lambda: q1_step(kernel_packs)),
+    ]
 for _, fn in VARIANTS:  # warm-up: state allocation, code objects
     fn()
 torch.cuda.synchronize()
@@ -148,11 +202,23 @@ out = {"bench": "diloco_sync", "zoo": size, "tensors": len(shapes), "numel": num
        "alpha": ALPHA}
 for name, _ in VARIANTS:
     out[name] = stats(ms[name])
-a, b = out["A_unfused_sequence"]["median_ms"], out["B_fused_sync"]["median_ms"]
 pg_ms = out["pseudograd_kernel"]["median_ms"]
 os_ms = out["outer_step_kernel"]["median_ms"]
+if args.quantized:
+    # bf16 bytes per element: 2 + 2 read, 1 written; g, l, m read and written, 1 code read
+    q0, q1 = out["Q0_quantized_fused_sequence"], out["Q1_fused_fp8_pack"]
+    out.update({
+        "Q1_over_Q0": round(q1["median_ms"] / q0["median_ms"], 3),
+        "Q_ranges_overlap": q1["max_ms"] >= q0["min_ms"] and q0["max_ms"] >= q1["min_ms"],
+        "pseudograd_fp8_tb_per_s": round(
+            5 * numel / out["pseudograd_fp8_kernel"]["median_ms"] / 1e9, 3),
+        "outer_step_fp8_tb_per_s": round(
+            13 * numel / out["outer_step_fp8_kernel"]["median_ms"] / 1e9, 3),
+    })
+else:
+    a, b = out["A_unfused_sequence"]["median_ms"], out["B_fused_sync"]["median_ms"]
+    out["B_over_A"] = round(b / a, 3)
 out.update({
-    "B_over_A": round(b / a, 3),
     "pseudograd_gb": round(3 * numel * 2 / 1e9, 3),
     "pseudograd_tb_per_s": round(3 * numel * 2 / pg_ms / 1e9, 3),
     "outer_step_gb": round(7 * numel * 2 / 1e9, 3),

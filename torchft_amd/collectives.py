@@ -7,6 +7,12 @@ at fp8 vs bf16 (8x vs fp32). On MI355X xGMI is 7 point-to-point links per
 GPU, so the alltoall+allgather decomposition engages all links instead of
 serializing on a single ring.
 
+``allreduce_pack`` is the same exchange for a caller that already holds the
+quantized pack and decodes the result itself (the fused DiLoCo outer sync,
+``ops.pseudograd_fp8_`` / ``ops.diloco_outer_step_fp8_``): alltoall → fused
+local reduce → allgather, in place on the pack, with no quantize or
+dequantize step around it.
+
 Reference parity (semantics): torchft/collectives.py:159-415.
 """
 
@@ -109,6 +115,52 @@ def allreduce_quantized(
         fut = fut.then(_dequant)
 
     return _QuantizedWork(fut, sync_stream, tensors)
+
+
+def allreduce_pack(
+    pack: torch.Tensor,
+    world: int,
+    op: ReduceOp,
+    pg: ProcessGroup,
+    sync_stream: Optional[torch.cuda.Stream] = None,
+) -> Work:
+    """The middle of ``allreduce_quantized`` on a pack the caller has already
+    quantized for ``world`` ranks (``ops.pseudograd_fp8_``), in place:
+    alltoall of the slices, fused reduce (requantizing) into the first slice
+    slot, allgather back into ``pack``. Nothing is quantized from or
+    dequantized into tensors; the caller decodes the pack
+    (``ops.diloco_outer_step_fp8_``). ``op`` is SUM or AVG as above."""
+    assert torch.cuda.is_available(), "the pack allreduce requires a HIP device"
+    if world != pg.size():
+        raise ValueError(
+            f"allreduce_pack: the pack was laid out for world {world}, the process "
+            f"group has {pg.size()} ranks"
+        )
+    slice_bytes = pack.numel() // world
+    if (pack.dtype != torch.uint8 or not pack.is_contiguous() or not pack.is_cuda
+            or slice_bytes * world != pack.numel() or slice_bytes % (4 + Q.QBLOCK)):
+        raise ValueError(
+            "allreduce_pack: pack must be a contiguous uint8 device tensor of "
+            f"{world} slices of whole blocks, got {pack.numel()} bytes"
+        )
+    avg = op == ReduceOp.AVG
+
+    if sync_stream is None:
+        sync_stream = torch.cuda.Stream()
+    sync_stream.wait_stream(torch.cuda.current_stream())
+
+    with torch.cuda.stream(sync_stream):
+        recv = torch.empty_like(pack)  # world copies of OUR slice
+        pg.alltoall_base(recv, pack, [], [], AllToAllOptions()).wait()
+
+        my_slice = pack.narrow(0, 0, slice_bytes)
+        Q.reduce_slices(recv, my_slice, world, avg)
+
+        ag_work = pg.allgather_into_tensor_coalesced([pack], [my_slice.clone()],
+                                                     AllgatherOptions())
+        fut = ag_work.get_future()
+
+    return _QuantizedWork(fut, sync_stream, [pack])
 
 
 def reduce_scatter_quantized(

@@ -29,6 +29,10 @@ MI355X notes: the outer allreduce can take the fp8-quantized path
 1 GiB default bucket is sized to saturate a per-link xGMI ring. With
 ``DiLoCo(fused_sync=True)`` the backups live in HBM instead and the outer sync
 runs through two multi-tensor HIP kernels (csrc/kernels/diloco_sync.hip).
+With ``fused_fp8_pack=True`` on top of both, the pseudo-gradient is quantized
+straight into the fp8 wire pack, the pack is what the manager reduces
+(``Manager.allreduce_pack``) and the outer step decodes it: no pseudo-gradient
+in the parameters' dtype is ever stored.
 """
 
 from __future__ import annotations
@@ -284,6 +288,19 @@ class _BucketPlan:
             s.tensor.copy_(flat[s.offset : s.offset + s.numel].view_as(s.tensor))
 
 
+@dataclass
+class _FusedPack:
+    """One bucket of a ``fused_fp8_pack`` sync: the fp8 wire pack of its
+    pseudo-gradients, the geometry it was laid out for, and where each
+    parameter's blocks start in it."""
+
+    pack: torch.Tensor
+    world: int
+    total_blocks: int
+    num_participants: int
+    first_block: Dict[str, int]
+
+
 # ---------------------------------------------------------------------------
 # DiLoCo fragments
 # ---------------------------------------------------------------------------
@@ -313,6 +330,14 @@ class _StreamingDiLoCoFragment:
     are read from ``param_groups`` at every outer step and its own
     ``momentum_buffer`` state is updated in place, but ``step()`` itself is
     never called, so step hooks registered on it do not fire.
+
+    With ``fused_fp8_pack=True`` as well (needs ``should_quantize=True``)
+    ``stage()`` is one launch per bucket that quantizes ``original - local``
+    into a fresh fp8 pack (``ops.pseudograd_fp8_``) and one
+    ``manager.allreduce_pack`` per pack; the committed outer step is one
+    launch per (param group, pack) that reads the averaged pseudo-gradient
+    from the reduced pack (``ops.diloco_outer_step_fp8_``). The packs are kept
+    until ``commit()`` and dropped there, committed or not.
     """
 
     bucket_cap_mb: int = 1 * 1024 * 1024 * 1024
@@ -335,11 +360,19 @@ class _StreamingDiLoCoFragment:
         fragment_sync_delay: int = 0,
         fragment_update_alpha: float = 0.0,
         fused_sync: bool = False,
+        fused_fp8_pack: bool = False,
     ) -> None:
         if fragment_sync_offset > sync_every:
             raise ValueError("Fragment must be synced once before `sync_every` steps")
         assert sync_every >= 1
+        if fused_fp8_pack and not (fused_sync and should_quantize):
+            raise ValueError(
+                "fused_fp8_pack needs fused_sync=True and should_quantize=True"
+            )
 
+        self._fused_fp8_pack = fused_fp8_pack
+        # fp8-pack mode: the packs of the sync in flight, one per bucket
+        self._fused_packs: List[_FusedPack] = []
         self._fused_sync = fused_sync
         if fused_sync:
             backup_device = self._check_fused(
@@ -534,6 +567,9 @@ class _StreamingDiLoCoFragment:
         if self._fused_plan is None:
             self._fused_plan = _BucketPlan(params, self.bucket_cap_mb, align_bytes=16)
         plan = self._fused_plan
+        if self._fused_fp8_pack:
+            self._prepare_sync_fp8_pack(plan, names, params)
+            return
         assert not self._fused_buckets
         self._fused_buckets = [plan.allocate(slots) for slots in plan.buckets]
         views = [v for _, vs in self._fused_buckets for v in vs]
@@ -550,9 +586,49 @@ class _StreamingDiLoCoFragment:
                     self._manager.allreduce(flat, should_quantize=self.should_quantize)
                 )
 
+    def _prepare_sync_fp8_pack(
+        self, plan: _BucketPlan, names: List[str], params: List[torch.Tensor]
+    ) -> None:
+        """Phase 1 with ``fused_fp8_pack``: per bucket of the plan one launch
+        quantizes ``original - local`` straight into a fresh fp8 wire pack
+        (the bucket's parameters are its tensor list, each padded to whole
+        blocks), then one pack allreduce per bucket. No pseudo-gradient in the
+        parameters' dtype exists at any point."""
+        from torchft_amd import ops
+        from torchft_amd import quantization as Q
+
+        assert not self._fused_packs and not self._inflight
+        # the pack's geometry depends on the world the quorum settled on
+        world = self._manager.pack_world()
+        participants = self._manager.num_participants()
+        start = 0
+        for slots in plan.buckets:
+            idx = range(start, start + len(slots))
+            start += len(slots)
+            local = [params[i] for i in idx]
+            total, _, _, slice_bytes = Q.pack_geometry(local, world)
+            # empty: the kernel writes every byte, padding slots included
+            pack = torch.empty(world * slice_bytes, dtype=torch.uint8, device=plan.device)
+            ops.pseudograd_fp8_(
+                pack, [self.original_parameters[names[i]] for i in idx], local, world
+            )
+            first, b = {}, 0
+            for i in idx:
+                first[names[i]] = b
+                b += (params[i].numel() + Q.QBLOCK - 1) // Q.QBLOCK
+            self._fused_packs.append(_FusedPack(pack, world, total, participants, first))
+
+        if self._stream is not None:
+            self._stream.wait_stream(torch.cuda.current_stream())
+        with self._side_stream():
+            for fp in self._fused_packs:
+                self._inflight.append(self._manager.allreduce_pack(fp.pack, fp.world))
+
     def _outer_step_fused(self) -> None:
         """Phase 3, fused: per param group one launch does the SGD step on
-        the snapshot, the re-snapshot and the merge of local progress."""
+        the snapshot, the re-snapshot and the merge of local progress (with
+        ``fused_fp8_pack`` one per param group and pack, reading the
+        pseudo-gradient from the reduced pack)."""
         from torchft_amd import ops
 
         by_param = {id(p): name for name, p in self._named_params()}
@@ -578,6 +654,28 @@ class _StreamingDiLoCoFragment:
                         # zeros: mu*0 + d == d, torch's clone-on-first-step
                         state["momentum_buffer"] = torch.zeros_like(p.data)
                     bufs.append(state["momentum_buffer"])
+            if self._fused_fp8_pack:
+                # the group's parameters that travelled in each pack
+                names = [by_param[id(p)] for p in mine]
+                for fp in self._fused_packs:
+                    sel = [i for i, name in enumerate(names) if name in fp.first_block]
+                    if not sel:
+                        continue
+                    ops.diloco_outer_step_fp8_(
+                        [self.original_parameters[names[i]] for i in sel],
+                        [mine[i].data for i in sel],
+                        fp.pack,
+                        [fp.first_block[names[i]] for i in sel],
+                        fp.total_blocks,
+                        fp.world,
+                        [bufs[i] for i in sel] if bufs is not None else None,
+                        lr=float(group["lr"]),
+                        momentum=momentum,
+                        nesterov=bool(group["nesterov"]),
+                        alpha=self._fragment_update_alpha,
+                        num_participants=fp.num_participants,
+                    )
+                continue
             ops.diloco_outer_step_(
                 [self.original_parameters[by_param[id(p)]] for p in mine],
                 [p.data for p in mine],
@@ -644,6 +742,7 @@ class _StreamingDiLoCoFragment:
                 self.restore_parameters()
             self._outer_optimizer.zero_grad()
             self._fused_buckets = []
+            self._fused_packs = []
             return committed
 
         # keep local progress for the merge, then roll back to the globals
@@ -727,6 +826,14 @@ class DiLoCo:
     this mode, so its step hooks do not fire; its ``momentum_buffer`` state is
     the one updated. DTensor parameters, a CPU-resident snapshot and other
     outer optimizers are not supported in fused mode.
+
+    ``fused_fp8_pack=True`` (opt-in; needs ``fused_sync=True`` and
+    ``should_quantize=True``, anything else raises ``ValueError``) keeps the
+    pseudo-gradient in the fp8 wire pack from end to end: one launch per
+    bucket quantizes ``original - local`` straight into the pack
+    (``ops.pseudograd_fp8_``), ``Manager.allreduce_pack`` reduces the pack in
+    place, and the outer step decodes it (``ops.diloco_outer_step_fp8_``). The
+    parameters and their snapshots must start on 16 B boundaries.
     """
 
     def __init__(
@@ -744,6 +851,7 @@ class DiLoCo:
         fragment_sync_delay: int = 0,
         fragment_update_alpha: float = 0.0,
         fused_sync: bool = False,
+        fused_fp8_pack: bool = False,
     ) -> None:
         n = len(model_fragments)
         if isinstance(outer_optimizer, list) and len(outer_optimizer) != n:
@@ -790,6 +898,7 @@ class DiLoCo:
                 fragment_sync_delay,
                 fragment_update_alpha,
                 fused_sync=fused_sync,
+                fused_fp8_pack=fused_fp8_pack,
             )
             for i, frag in enumerate(model_fragments)
         ]

@@ -486,6 +486,41 @@ class Manager:
             managed._append(normalize)
         return managed
 
+    def pack_world(self) -> int:
+        """The world an fp8 pack for ``allreduce_pack`` must be laid out for:
+        the process group's size once the quorum has configured it."""
+        self.wait_quorum()
+        return self._pg.size()
+
+    @torch.profiler.record_function("torchft_amd::manager::allreduce_pack")
+    def allreduce_pack(self, pack: torch.Tensor, world: int) -> Work:
+        """Fault-tolerant SUM allreduce of an already quantized fp8 pack, in
+        place (``collectives.allreduce_pack``), laid out for ``world =
+        pack_world()`` ranks. Same contract as ``allreduce``: on any error the
+        work still "succeeds" and the step fails at ``should_commit``. There
+        is no normalization: the caller divides by ``num_participants()`` when
+        it decodes the pack (``ops.diloco_outer_step_fp8_``)."""
+        if self.errored():
+            return _DummyWork(pack)
+
+        self.wait_quorum()
+
+        if not self.is_participating():
+            pack.zero_()  # scales 0, codes 0: a valid pack of zeros
+
+        try:
+            from torchft_amd.collectives import allreduce_pack
+
+            work = allreduce_pack(
+                pack, world, ReduceOp.SUM, self._pg, torch.cuda.current_stream()
+            )
+        except Exception as e:  # noqa: BLE001
+            self._logger.exception(f"allreduce_pack failed to launch: {e}")
+            self.report_error(e)
+            return _DummyWork(pack)
+
+        return _ManagedWork(self, work, pack)
+
     def report_error(self, e: Exception) -> None:
         """Mark the in-flight step failed; its gradients must be discarded."""
         self._attempt.error = ExceptionWithTraceback(e)

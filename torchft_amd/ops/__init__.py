@@ -1,7 +1,8 @@
 """CDNA4 fused ops: RMSNorm, RoPE, the fused QKV split + RoPE (``qkv_rope``,
 with per-token positions for packed rows), SwiGLU, fused AdamW (with optional fused
 global-norm clipping), gradient norm / clip, the fused loss head and the
-fused DiLoCo outer sync (``pseudograd_``, ``diloco_outer_step_``).
+fused DiLoCo outer sync (``pseudograd_``, ``diloco_outer_step_``, and
+``pseudograd_fp8_`` / ``diloco_outer_step_fp8_`` around the fp8 wire pack).
 
 On a HIP device these route through the in-tree gfx950 extension
 (``torchft_amd/_hip_kernels.so``, sources in ``csrc/kernels/``) and FAIL
@@ -593,7 +594,12 @@ from torchft_amd.ops.cross_entropy import linear_cross_entropy  # noqa: E402,F40
 
 # ----------------------------------------------------------------- DiLoCo outer sync
 
-from torchft_amd.ops.diloco import diloco_outer_step_, pseudograd_  # noqa: E402,F401
+from torchft_amd.ops.diloco import (  # noqa: E402,F401
+    diloco_outer_step_,
+    diloco_outer_step_fp8_,
+    pseudograd_,
+    pseudograd_fp8_,
+)
 
 # ----------------------------------------------------------------- Flash attention
 

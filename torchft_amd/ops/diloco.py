@@ -29,6 +29,22 @@ Two in-place multi-tensor ops back ``DiLoCo(..., fused_sync=True)``
 
 All tensors of one call share one dtype (bf16, fp16 or fp32) and are
 contiguous; zero-numel tensors are skipped.
+
+With the fp8-quantized allreduce two more ops put the wire pack of
+``torchft_amd.quantization`` in place of the pseudo-gradient tensors, so the
+pseudo-gradient is never stored in the parameters' dtype
+(``DiLoCo(fused_sync=True, should_quantize=True, fused_fp8_pack=True)``):
+
+``pseudograd_fp8_(pack, minuends, subtrahends, world)``
+    ``pack = quantize_pack(float(minuends[i]) - float(subtrahends[i]))``: the
+    fp32 difference goes through the quantizer's block math unrounded, every
+    byte of the pack is written. On CPU this is ``quantize_pack_ref``.
+
+``diloco_outer_step_fp8_(snapshots, params, pack, first_blocks, ...)``
+    ``diloco_outer_step_`` with ``d = code * (scale * fl(1/num_participants))``
+    read from the reduced pack; tensor ``i`` owns the pack blocks from
+    ``first_blocks[i]`` on. On CPU: ``pack_values_ref`` and
+    ``diloco_outer_step_ref``.
 """
 
 from __future__ import annotations
@@ -145,13 +161,133 @@ def diloco_outer_step_(
             lr, momentum, bool(nesterov), alpha,
         )
         return
+    _outer_step_cpu(snapshots, params, pseudograds, momentum_bufs, lr, momentum,
+                    bool(nesterov), alpha)
+
+
+def _outer_step_cpu(snapshots, params, pseudograds, momentum_bufs, lr, momentum,
+                    nesterov, alpha) -> None:
+    """The definition, tensor by tensor, in place. ``pseudograds`` may be fp32
+    whatever the storage dtype is (the decoded pack)."""
     for i, (g, l, d) in enumerate(zip(snapshots, params, pseudograds)):  # noqa: E741
         m = momentum_bufs[i] if momentum_bufs is not None else None
         m_new, g_new, p = diloco_outer_step_ref(
             g, d.view_as(g), m.view_as(g) if m is not None else None, l.view_as(g),
-            lr=lr, momentum=momentum, nesterov=bool(nesterov), alpha=alpha,
+            lr=lr, momentum=momentum, nesterov=nesterov, alpha=alpha,
         )
         if m is not None:
             m.copy_(m_new.view_as(m))
         g.copy_(g_new)
         l.copy_(p.view_as(l))
+
+
+# ----------------------------------------------------------- through the fp8 pack
+
+
+def _blocks(t: torch.Tensor) -> int:
+    from torchft_amd.quantization import QBLOCK
+
+    return (t.numel() + QBLOCK - 1) // QBLOCK
+
+
+def _check_pack(what: str, pack: torch.Tensor, like: torch.Tensor, total_blocks: int,
+                world: int) -> int:
+    """The rules of the bindings, for the CPU path too. Returns the bytes of
+    the pack's ``world`` slices."""
+    from torchft_amd.quantization import QBLOCK
+
+    if world < 1:
+        raise ValueError(f"{what}: world must be >= 1, got {world}")
+    need = -(-total_blocks // world) * (4 + QBLOCK) * world
+    if pack.dtype != torch.uint8 or not pack.is_contiguous() or pack.dim() != 1:
+        raise ValueError(f"{what}: pack must be a contiguous 1-D uint8 tensor")
+    if pack.device != like.device:
+        raise ValueError(f"{what}: pack must be on the tensors' device ({like.device})")
+    if pack.numel() < need:
+        raise ValueError(f"{what}: pack holds {pack.numel()} bytes, needs {need}")
+    return need
+
+
+@torch.no_grad()
+def pseudograd_fp8_(
+    pack: torch.Tensor,
+    minuends: Sequence[torch.Tensor],
+    subtrahends: Sequence[torch.Tensor],
+    world: int,
+) -> None:
+    """``pack`` = the fp8 wire pack (``quantization.allocate_pack(minuends,
+    world)``) of ``minuends[i] - subtrahends[i]``, the difference taken in
+    fp32 and quantized from there. On a HIP device every tensor must start on
+    a 16 B boundary."""
+    what = "pseudograd_fp8_"
+    _check_lists(what, (minuends, subtrahends))
+    need = _check_pack(what, pack, minuends[0], sum(_blocks(t) for t in minuends), world)
+    if pack.is_cuda:
+        hip_ext().diloco_pseudograd_fp8(list(minuends), list(subtrahends), pack, world)
+        return
+    from torchft_amd.quantization import quantize_pack_ref
+
+    diffs = [a.float() - b.float() for a, b in zip(minuends, subtrahends)]
+    pack[:need].copy_(quantize_pack_ref(diffs, world))
+
+
+@torch.no_grad()
+def diloco_outer_step_fp8_(
+    snapshots: Sequence[torch.Tensor],
+    params: Sequence[torch.Tensor],
+    pack: torch.Tensor,
+    first_blocks: Sequence[int],
+    pack_total_blocks: int,
+    world: int,
+    momentum_bufs: Optional[Sequence[torch.Tensor]],
+    *,
+    lr: float,
+    momentum: float,
+    nesterov: bool,
+    alpha: float,
+    num_participants: int,
+) -> None:
+    """``diloco_outer_step_`` for one param group whose averaged
+    pseudo-gradients are read from ``pack``, the SUM-reduced wire pack of
+    ``pack_total_blocks`` blocks over ``world`` slices: tensor ``i`` owns the
+    blocks from ``first_blocks[i]`` on, and its pseudo-gradient is
+    ``code * (scale * fl(1 / num_participants))``. The pack is not modified."""
+    what = "diloco_outer_step_fp8_"
+    lr, momentum, alpha = float(lr), float(momentum), float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must be between 0 and 1, got {alpha}")
+    if num_participants < 1:
+        raise ValueError(f"{what}: num_participants must be >= 1, got {num_participants}")
+    lists: List[Sequence[torch.Tensor]] = [snapshots, params]
+    if momentum != 0:
+        if momentum_bufs is None:
+            raise ValueError(f"{what}: momentum != 0 needs momentum_bufs")
+        lists.append(momentum_bufs)
+    else:
+        momentum_bufs = None
+    _check_lists(what, lists)
+    need = _check_pack(what, pack, snapshots[0], pack_total_blocks, world)
+    first_blocks = [int(b) for b in first_blocks]
+    if len(first_blocks) != len(snapshots):
+        raise ValueError(f"{what}: first_blocks needs one entry per tensor")
+    for i, (b, t) in enumerate(zip(first_blocks, snapshots)):
+        if b < 0 or b + _blocks(t) > pack_total_blocks:
+            raise ValueError(
+                f"{what}: first_blocks[{i}] = {b} puts a tensor of {_blocks(t)} blocks "
+                f"outside the pack's {pack_total_blocks}"
+            )
+    inv_div = float(torch.tensor(1.0, dtype=torch.float32) / num_participants)
+    if pack.is_cuda:
+        hip_ext().diloco_outer_step_fp8(
+            list(snapshots), list(params), pack, first_blocks, pack_total_blocks, world,
+            list(momentum_bufs) if momentum_bufs is not None else [],
+            lr, momentum, bool(nesterov), alpha, inv_div,
+        )
+        return
+    from torchft_amd.quantization import pack_values_ref
+
+    vals = pack_values_ref(pack[:need], world, inv_div)
+    ds = [vals[b : b + _blocks(t)].reshape(-1)[: t.numel()]
+          for b, t in zip(first_blocks, snapshots)]
+    _outer_step_cpu(snapshots, params, ds, momentum_bufs, lr, momentum, bool(nesterov),
+                    alpha)

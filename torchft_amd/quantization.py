@@ -154,6 +154,15 @@ def dequantize_pack_ref(
     return out
 
 
+def pack_values_ref(pack: torch.Tensor, world: int, inv_div: float = 1.0) -> torch.Tensor:
+    """Every block of a pack decoded as the outer step from a pack decodes it:
+    ``code * (scale * inv_div)``, two fp32 products, as [padded_blocks, QBLOCK]
+    fp32 in pack-block order (tensor t's rows start at its first block)."""
+    scales, codes = split_slices(pack, world)
+    s = scales.reshape(-1) * torch.tensor(inv_div, dtype=torch.float32, device=pack.device)
+    return e4m3_values(codes.reshape(-1, QBLOCK)) * s[:, None]
+
+
 def reduce_slices_ref(recv: torch.Tensor, world: int, avg: bool,
                       fused: bool = False) -> torch.Tensor:
     """The fused reduce on `world` received slices: fp32 accumulation of
