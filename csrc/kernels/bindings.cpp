@@ -559,23 +559,76 @@ at::Tensor qkv_rope_bwd(at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor 
 
 // ---- fused AdamW ------------------------------------------------------------
 
+namespace {
+
+// The rounding mode of an adamw_step / adamw_clip_step call (kernels.h,
+// AdamwRounding) and the one list it brings: `masters` for kRoundMaster,
+// `stream_ids` for kRoundStochastic, the other empty. The list becomes one more
+// table column, so TableSet holds it to the rule of every column.
+struct RoundingArgs {
+  int mode;
+  const TensorList* masters;
+  const std::vector<int64_t>* stream_ids;
+
+  RoundingArgs(const char* what, int64_t rounding, const TensorList& masters_,
+               const std::vector<int64_t>& stream_ids_)
+      : mode((int)rounding), masters(&masters_), stream_ids(&stream_ids_) {
+    TORCH_CHECK(rounding == tft::kRoundNearest || rounding == tft::kRoundStochastic ||
+                    rounding == tft::kRoundMaster,
+                what, ": rounding must be 0 (nearest), 1 (stochastic) or 2 (master), got ",
+                rounding);
+    TORCH_CHECK(masters_.empty() || mode == tft::kRoundMaster, what,
+                ": masters are given with rounding = 2 (master) only");
+    TORCH_CHECK(stream_ids_.empty() || mode == tft::kRoundStochastic, what,
+                ": stream_ids are given with rounding = 1 (stochastic) only");
+    for (size_t i = 0; i < stream_ids_.size(); i++)
+      TORCH_CHECK(stream_ids_[i] >= 0 && stream_ids_[i] <= (int64_t)UINT32_MAX, what,
+                  ": stream_ids[", i, "] = ", stream_ids_[i], " is not a 32-bit number");
+  }
+
+  // the Philox key (the 64-bit seed) and the plain mode's step word; the
+  // counter keeps the step count's low 32 bits
+  static tft::SrKey key(int64_t sr_seed, int64_t step) {
+    const uint64_t seed = (uint64_t)sr_seed;
+    return tft::SrKey{(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step};
+  }
+
+  // the mode's column behind `cols`, if it has one
+  void add_column(std::vector<Column>& cols) const {
+    if (mode == tft::kRoundMaster) cols.push_back({masters, at::kFloat, false, "masters"});
+    if (mode == tft::kRoundStochastic)
+      cols.push_back({nullptr, at::kLong, false, "stream_ids", stream_ids});
+  }
+};
+
+}  // namespace
+
 void adamw_step(const std::vector<at::Tensor>& params,
                 const std::vector<at::Tensor>& grads,
                 const std::vector<at::Tensor>& exp_avgs,
                 const std::vector<at::Tensor>& exp_avg_sqs, double lr,
                 double beta1, double beta2, double eps, double weight_decay,
-                int64_t step) {
+                int64_t step, int64_t rounding, const std::vector<at::Tensor>& masters,
+                const std::vector<int64_t>& stream_ids, int64_t sr_seed) {
   TORCH_CHECK(!params.empty(), "adamw_step: need at least one tensor");
+  const RoundingArgs ra("adamw_step", rounding, masters, stream_ids);
   TableSet tables(params[0], "adamw_step");
-  const int h = tables.add({{&params, at::kBFloat16},
-                            {&grads, at::kBFloat16},
-                            {&exp_avgs, at::kFloat},
-                            {&exp_avg_sqs, at::kFloat}});
+  std::vector<Column> cols = {{&params, at::kBFloat16},
+                              {&grads, at::kBFloat16},
+                              {&exp_avgs, at::kFloat},
+                              {&exp_avg_sqs, at::kFloat}};
+  ra.add_column(cols);
+  const int h = tables.add(cols);
   tables.upload();
   const float bc1 = 1.0f - std::pow((float)beta1, (float)step);
   const float bc2 = 1.0f - std::pow((float)beta2, (float)step);
-  tft::launch_adamw(tables.table(h), (float)lr, (float)beta1, (float)beta2, (float)eps,
-                    (float)weight_decay, bc1, bc2, current_stream());
+  if (ra.mode == tft::kRoundNearest)
+    tft::launch_adamw(tables.table(h), (float)lr, (float)beta1, (float)beta2, (float)eps,
+                      (float)weight_decay, bc1, bc2, current_stream());
+  else
+    tft::launch_adamw_rounded(ra.mode, tables.table(h), (float)lr, (float)beta1,
+                              (float)beta2, (float)eps, (float)weight_decay, bc1, bc2,
+                              RoundingArgs::key(sr_seed, step), current_stream());
 }
 
 // ---- global gradient norm / clip ---------------------------------------------
@@ -683,7 +736,14 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
                      const std::vector<double>& epss,
                      const std::vector<double>& weight_decays, double max_norm,
                      int64_t max_blocks, at::Tensor stats, at::Tensor skipped,
-                     at::Tensor norm_out, py::object norm_reduce) {
+                     at::Tensor norm_out, py::object norm_reduce, int64_t rounding,
+                     const std::vector<at::Tensor>& masters,
+                     const std::vector<int64_t>& stream_ids,
+                     const std::vector<int64_t>& sr_seeds) {
+  const RoundingArgs ra("adamw_clip_step", rounding, masters, stream_ids);
+  TORCH_CHECK(ra.mode != tft::kRoundStochastic || sr_seeds.size() == group_sizes.size(),
+              "adamw_clip_step: sr_seeds needs one seed per param group, got ",
+              sr_seeds.size(), " for ", group_sizes.size());
   const int64_t n = (int64_t)params.size();
   const int64_t ng = (int64_t)group_sizes.size();
   TORCH_CHECK(n > 0, "adamw_clip_step: need at least one tensor");
@@ -709,12 +769,13 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
   int64_t first = 0;
   for (int64_t g = 0; g < ng; g++) {
     TORCH_CHECK(group_sizes[g] >= 0 && first + group_sizes[g] <= n);
-    h_update[g] = tables.add({{&params, at::kBFloat16},
-                              {&grads, at::kBFloat16},
-                              {&exp_avgs, at::kFloat},
-                              {&exp_avg_sqs, at::kFloat},
-                              {&steps, at::kInt, /*one_element=*/true}},
-                             first, group_sizes[g]);
+    std::vector<Column> cols = {{&params, at::kBFloat16},
+                                {&grads, at::kBFloat16},
+                                {&exp_avgs, at::kFloat},
+                                {&exp_avg_sqs, at::kFloat},
+                                {&steps, at::kInt, /*one_element=*/true}};
+    ra.add_column(cols);
+    h_update[g] = tables.add(cols, first, group_sizes[g]);
     first += group_sizes[g];
   }
   TORCH_CHECK(first == n, "group_sizes must cover every tensor");
@@ -725,10 +786,19 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
   run_sumsq({{tft::kBF16, tables.table(h_norm)}}, max_blocks, stats, stream);
   if (!norm_reduce.is_none()) norm_reduce(stats.narrow(0, 0, 1));
 
-  for (int64_t g = 0; g < ng; g++)
-    tft::launch_adamw_clip(tables.table(h_update[g]), (float)lrs[g], (float)beta1s[g],
-                           (float)beta2s[g], (float)epss[g], (float)weight_decays[g],
-                           stats.data_ptr<float>(), (float)max_norm, stream);
+  for (int64_t g = 0; g < ng; g++) {
+    if (ra.mode == tft::kRoundNearest)
+      tft::launch_adamw_clip(tables.table(h_update[g]), (float)lrs[g], (float)beta1s[g],
+                             (float)beta2s[g], (float)epss[g], (float)weight_decays[g],
+                             stats.data_ptr<float>(), (float)max_norm, stream);
+    else
+      tft::launch_adamw_clip_rounded(ra.mode, tables.table(h_update[g]), (float)lrs[g],
+                                     (float)beta1s[g], (float)beta2s[g], (float)epss[g],
+                                     (float)weight_decays[g], stats.data_ptr<float>(),
+                                     (float)max_norm,
+                                     RoundingArgs::key(sr_seeds.empty() ? 0 : sr_seeds[g], 0),
+                                     stream);
+  }
   const auto st = tables.table(h_steps);
   tft::launch_adamw_bump_steps(st.col(0), st.n, stats.data_ptr<float>(),
                                skipped.data_ptr<int>(), norm_out.data_ptr<float>(),
@@ -1087,8 +1157,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qkv_rope_bwd", &qkv_rope_bwd, py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("cos_tab"), py::arg("sin_tab"), py::arg("positions") = py::none(),
         "transpose of qkv_rope_fwd: returns dqkv [B, S, (Hq + 2 * Hkv) * D]");
-  m.def("adamw_step", &adamw_step);
-  m.def("adamw_clip_step", &adamw_clip_step,
+  // rounding: 0 nearest, 1 stochastic (with stream_ids and sr_seed), 2 master
+  // (with masters)
+  m.def("adamw_step", &adamw_step, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("weight_decay"), py::arg("step"), py::arg("rounding") = 0,
+        py::arg("masters") = std::vector<at::Tensor>(),
+        py::arg("stream_ids") = std::vector<int64_t>(), py::arg("sr_seed") = 0);
+  m.def("adamw_clip_step", &adamw_clip_step, py::arg("params"), py::arg("grads"),
+        py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("steps"),
+        py::arg("group_sizes"), py::arg("lrs"), py::arg("beta1s"), py::arg("beta2s"),
+        py::arg("epss"), py::arg("weight_decays"), py::arg("max_norm"),
+        py::arg("max_blocks"), py::arg("stats"), py::arg("skipped"), py::arg("norm_out"),
+        py::arg("norm_reduce"), py::arg("rounding") = 0,
+        py::arg("masters") = std::vector<at::Tensor>(),
+        py::arg("stream_ids") = std::vector<int64_t>(),
+        py::arg("sr_seeds") = std::vector<int64_t>(),
         "FusedAdamW step with fused global-norm clip and non-finite skip");
   m.def("grad_sumsq", &grad_sumsq,
         "global sum of squares of a tensor list: 1-element fp32 device tensor");

@@ -13,10 +13,21 @@
 #include <hip/hip_runtime.h>
 
 #include "multi_tensor.h"
+#include "philox.h"
 
 namespace torchft_amd {
 
 using bf16 = __hip_bfloat16;
+
+// bf16 bits of v rounded at random with r16 (philox.h); inf and NaN are stored
+// as from_f32 stores them: added bits could carry a NaN out of the NaNs
+__device__ inline uint32_t sr_bits(float v, uint32_t r16) {
+  const uint32_t b = __float_as_uint(v);
+  if (sr_finite(b)) return sr_bf16(b, r16);
+  bf16 t;
+  from_f32(&t, v);
+  return __bfloat16_as_ushort(t);
+}
 
 // Table columns: 0 param, 1 grad (bf16), 2 exp_avg, 3 exp_avg_sq (fp32) and,
 // in clip mode, 4 the device step counts. kClip = false is the plain step:
@@ -26,10 +37,30 @@ using bf16 = __hip_bfloat16;
 // leaves p/m/v untouched, and the bias corrections come from the per-tensor
 // device step counts (bumped afterwards by adamw_bump_steps_kernel), so a
 // skipped step costs no host sync and no bias-correction step.
-template <bool kClip>
+//
+// kRound (kernels.h, AdamwRounding; docs/KERNELS.md, "Rounding modes") is how
+// p' reaches memory, the arithmetic of the step being one expression for all:
+//   kRoundNearest     one round-to-nearest bf16 store. `key` is an empty pack,
+//                     so these two instantiations have the argument list, and
+//                     the ISA, they had before the template parameter.
+//   kRoundStochastic  p' is rounded up or down at random, E[stored] = p'. The
+//                     lane's 8 x 16 bits are one Philox4x32-10 call: counter
+//                     {off / 8 low, high, step count being taken, stream id
+//                     (the next column, a number)}, key = the seed (`key` is
+//                     one SrKey). Nothing of the launch enters, so a tensor
+//                     draws the same bits on the 16 B and the element path, in
+//                     any table or block, and again when a skipped step is
+//                     retried.
+//   kRoundMaster      the next column is the fp32 master copy. It is the
+//                     truth wherever bf16(master) has the bits of the stored
+//                     p; elsewhere someone wrote p behind the optimizer's back
+//                     and float(p) is. The step runs on that value, stores it
+//                     as the new master and p = bf16(master).
+template <bool kClip, int kRound, typename... Key>
 __global__ void adamw_kernel(MultiTensorTable tb, float lr, float beta1, float beta2,
                              float eps, float weight_decay, float bc1, float bc2,
-                             const float* __restrict__ stats, float max_norm) {
+                             const float* __restrict__ stats, float max_norm, Key... key) {
+  constexpr int kExtraCol = kClip ? 5 : 4;
   float coef = 1.f;
   if constexpr (kClip) {
     const float norm = sqrtf(stats[0]);
@@ -39,8 +70,10 @@ __global__ void adamw_kernel(MultiTensorTable tb, float lr, float beta1, float b
   const MtCursor c(tb, blockIdx.x, threadIdx.x);
   const int cnt = c.cnt;
   if (cnt == 0) return;
+  int32_t taking = 0;  // the step count being taken, clip mode
   if constexpr (kClip) {
-    const float s = (float)(*reinterpret_cast<const int32_t*>(c.addr(tb, 4)) + 1);
+    taking = *reinterpret_cast<const int32_t*>(c.addr(tb, 4)) + 1;
+    const float s = (float)taking;
     bc1 = 1.f - powf(beta1, s);
     bc2 = 1.f - powf(beta2, s);
   }
@@ -52,20 +85,38 @@ __global__ void adamw_kernel(MultiTensorTable tb, float lr, float beta1, float b
   float* m = c.at<float>(am);
   float* v = c.at<float>(av);
 
-  const bool full = c.vec_ok(ap | ag | am | av);
+  int64_t aw = 0;
+  if constexpr (kRound == kRoundMaster) aw = c.addr(tb, kExtraCol);
+  float* w = c.at<float>(aw);
+
+  const bool full = c.vec_ok(ap | ag | am | av | aw);
 
   float pv[kMtEpt], gv[kMtEpt], mv[kMtEpt], vv[kMtEpt];
+  [[maybe_unused]] float wv[kMtEpt];
   if (full) {
     load8(p, pv);
     load8(g, gv);
     load8(m, mv);
     load8(v, vv);
+    if constexpr (kRound == kRoundMaster) load8(w, wv);
   } else {
     for (int i = 0; i < cnt; i++) {
       pv[i] = to_f32(p[i]);
       gv[i] = to_f32(g[i]);
       mv[i] = m[i];
       vv[i] = v[i];
+      if constexpr (kRound == kRoundMaster) wv[i] = w[i];
+    }
+  }
+
+  if constexpr (kRound == kRoundMaster) {
+    // per element, no flag and no sync; a NaN on either side compares unequal
+    // or equal and is a NaN whichever is taken
+#pragma unroll
+    for (int i = 0; i < kMtEpt; i++) {
+      if (!full && i >= cnt) break;
+      if (__float_as_uint(d_round((bf16*)nullptr, wv[i])) == __float_as_uint(pv[i]))
+        pv[i] = wv[i];
     }
   }
 
@@ -93,15 +144,45 @@ __global__ void adamw_kernel(MultiTensorTable tb, float lr, float beta1, float b
     pv[i] -= lr * (mhat / (sqrtf(vhat) + eps) + weight_decay * pv[i]);
   }
 
+  if constexpr (kRound == kRoundStochastic) {
+    const SrKey k{key...};
+    const uint64_t vec = (uint64_t)c.off / kMtEpt;
+    const Philox4 r = philox4x32_10(
+        Philox4{{(uint32_t)vec, (uint32_t)(vec >> 32), kClip ? (uint32_t)taking : k.step,
+                 (uint32_t)c.addr(tb, kExtraCol)}},
+        k.seed_lo, k.seed_hi);
+    if (full) {
+      uint32_t raw[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        raw[i] = sr_bits(pv[2 * i], philox_r16(r, 2 * i)) |
+                 sr_bits(pv[2 * i + 1], philox_r16(r, 2 * i + 1)) << 16;
+      *reinterpret_cast<uint4*>(p) = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+      store8(m, mv);
+      store8(v, vv);
+    } else {
+#pragma unroll
+      for (int i = 0; i < kMtEpt; i++) {
+        if (i >= cnt) break;
+        p[i] = __ushort_as_bfloat16((unsigned short)sr_bits(pv[i], philox_r16(r, i)));
+        m[i] = mv[i];
+        v[i] = vv[i];
+      }
+    }
+    return;
+  }
+
   if (full) {
     store8(p, pv);
     store8(m, mv);
     store8(v, vv);
+    if constexpr (kRound == kRoundMaster) store8(w, pv);
   } else {
     for (int i = 0; i < cnt; i++) {
       from_f32(p + i, pv[i]);
       m[i] = mv[i];
       v[i] = vv[i];
+      if constexpr (kRound == kRoundMaster) w[i] = pv[i];
     }
   }
 }
@@ -110,7 +191,7 @@ void launch_adamw(MultiTensorTable tb, float lr, float beta1, float beta2,
                   float eps, float weight_decay, float bias_correction1,
                   float bias_correction2, hipStream_t stream) {
   if (tb.total_blocks <= 0) return;
-  hipLaunchKernelGGL(adamw_kernel<false>, dim3((uint32_t)tb.total_blocks),
+  hipLaunchKernelGGL((adamw_kernel<false, kRoundNearest>), dim3((uint32_t)tb.total_blocks),
                      dim3(kMtThreads), 0, stream, tb, lr, beta1, beta2, eps,
                      weight_decay, bias_correction1, bias_correction2,
                      (const float*)nullptr, 0.f);
@@ -138,9 +219,42 @@ void launch_adamw_clip(MultiTensorTable tb, float lr, float beta1, float beta2,
                        float eps, float weight_decay, const float* stats,
                        float max_norm, hipStream_t stream) {
   if (tb.total_blocks <= 0) return;
-  hipLaunchKernelGGL(adamw_kernel<true>, dim3((uint32_t)tb.total_blocks),
+  hipLaunchKernelGGL((adamw_kernel<true, kRoundNearest>), dim3((uint32_t)tb.total_blocks),
                      dim3(kMtThreads), 0, stream, tb, lr, beta1, beta2, eps,
                      weight_decay, 1.f, 1.f, stats, max_norm);
+}
+
+// kClip with the two modes that are not kRoundNearest
+template <bool kClip>
+static void launch_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, float bc1, float bc2,
+                           const float* stats, float max_norm, SrKey key,
+                           hipStream_t stream) {
+  if (tb.total_blocks <= 0) return;
+  const dim3 grid((uint32_t)tb.total_blocks), block(kMtThreads);
+  if (rounding == kRoundStochastic)
+    hipLaunchKernelGGL((adamw_kernel<kClip, kRoundStochastic, SrKey>), grid, block, 0, stream,
+                       tb, lr, beta1, beta2, eps, weight_decay, bc1, bc2, stats, max_norm,
+                       key);
+  else
+    hipLaunchKernelGGL((adamw_kernel<kClip, kRoundMaster>), grid, block, 0, stream, tb, lr,
+                       beta1, beta2, eps, weight_decay, bc1, bc2, stats, max_norm);
+}
+
+void launch_adamw_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
+                          float beta2, float eps, float weight_decay,
+                          float bias_correction1, float bias_correction2, SrKey key,
+                          hipStream_t stream) {
+  launch_rounded<false>(rounding, tb, lr, beta1, beta2, eps, weight_decay,
+                        bias_correction1, bias_correction2, nullptr, 0.f, key, stream);
+}
+
+void launch_adamw_clip_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
+                               float beta2, float eps, float weight_decay,
+                               const float* stats, float max_norm, SrKey key,
+                               hipStream_t stream) {
+  launch_rounded<true>(rounding, tb, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, stats,
+                       max_norm, key, stream);
 }
 
 void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,

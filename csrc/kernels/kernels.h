@@ -124,6 +124,26 @@ void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,
                              const float* stats, int32_t* skipped, float* norm_out,
                              tft_stream stream);
 
+// How the step stores the parameter (docs/KERNELS.md, "Rounding modes"). The
+// launchers above are kRoundNearest; the two below take the other modes, each
+// with one more table column after the mode's last (4 plain, 5 clip):
+// kRoundStochastic the parameter's stream id (a number, not an address, below
+// 2^32), kRoundMaster its fp32 master copy. `key` is read by kRoundStochastic
+// alone; the clip mode takes the step word from the device step count + 1.
+enum AdamwRounding : int { kRoundNearest = 0, kRoundStochastic = 1, kRoundMaster = 2 };
+struct SrKey {
+  uint32_t seed_lo, seed_hi;
+  uint32_t step;  // the step count being taken, plain mode
+};
+void launch_adamw_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
+                          float beta2, float eps, float weight_decay,
+                          float bias_correction1, float bias_correction2, SrKey key,
+                          tft_stream stream);
+void launch_adamw_clip_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
+                               float beta2, float eps, float weight_decay,
+                               const float* stats, float max_norm, SrKey key,
+                               tft_stream stream);
+
 // grad_norm.hip ------------------------------------------------------------
 // table: col 0 = the gradients. `grid` workgroups grid-stride over the
 // logical blocks and write partials[0..grid); finalize sums n_partials of

@@ -404,7 +404,33 @@ class FusedAdamW(torch.optim.Optimizer):
     the skips, both as device tensors. ``norm_reduce``, if given, is called
     with the 1-element fp32 sum of squares before the update; FSDP2/DTensor
     callers all-reduce (SUM) their shard's value there.
+
+    ``rounding`` is how the fp32 result of the step reaches a bf16 parameter
+    (docs/KERNELS.md, "Rounding modes"), in the plain and in the clip mode:
+
+    ``"nearest"`` (default)  one round-to-nearest store, 22 B/element. An update
+        below ``2^-9 |p|`` is dropped whole, step after step: fine while the
+        learning rate is large, a stall late in a decaying schedule, and
+        weight decay alone (``lr * wd`` of ``|p|``) never acts.
+    ``"stochastic"``  the store rounds up or down at random with the expected
+        value of the fp32 result, so small updates act on average. Same
+        memory and traffic as ``"nearest"``; for pure-bf16 training that
+        cannot afford four more bytes per parameter. The bits are
+        Philox4x32-10 of (``sr_seed``, step count, the parameter's index in
+        ``param_groups`` order, element index), so a run is reproducible and a
+        checkpoint continues it bit for bit.
+    ``"master"``  ``state[p]["master"]`` holds the parameter in fp32; the step
+        runs on it and ``p`` is its bf16 rounding: what FSDP2 / torchtitan
+        mixed precision gives, for 4 B/parameter more memory and 30 B/element
+        of traffic. Where ``p`` no longer is the rounding of ``master``
+        (DiLoCo's outer step, a heal, ``p.copy_()``), the step starts from
+        ``p``, element by element, so nobody has to tell the optimizer.
+
+    Parameters that are not bf16, and everything on the CPU, take the torch
+    path with the same semantics.
     """
+
+    ROUNDINGS = ("nearest", "stochastic", "master")
 
     def __init__(
         self,
@@ -415,9 +441,18 @@ class FusedAdamW(torch.optim.Optimizer):
         weight_decay: float = 0.01,
         max_grad_norm: Optional[float] = None,
         norm_reduce: Optional[Callable[[torch.Tensor], None]] = None,
+        rounding: str = "nearest",
+        sr_seed: int = 0,
     ) -> None:
+        if rounding not in self.ROUNDINGS:
+            raise ValueError(f"rounding must be one of {self.ROUNDINGS}, got {rounding!r}")
+        if not 0 <= int(sr_seed) < 2 ** 63:
+            raise ValueError(f"sr_seed must be in [0, 2**63), got {sr_seed}")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if rounding == "stochastic":
+            defaults["sr_seed"] = int(sr_seed)  # travels in state_dict()
         super().__init__(params, defaults)
+        self.rounding = rounding
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not max_grad_norm > 0:
@@ -444,6 +479,16 @@ class FusedAdamW(torch.optim.Optimizer):
         # torch leaves a "step" entry as it was saved (an int or a tensor on
         # any device); make it what this optimizer's mode steps with.
         super().load_state_dict(state_dict)
+        # torch casts every floating-point state tensor to the parameter's
+        # dtype; the moments and the master copy of a bf16 parameter are fp32
+        saved_ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        own = [p for g in self.param_groups for p in g["params"]]
+        for i, p in zip(saved_ids, own):
+            for key in ("exp_avg", "exp_avg_sq", "master"):
+                saved = state_dict["state"].get(i, {}).get(key)
+                if saved is not None:
+                    self.state[p][key] = saved.detach().to(
+                        device=_local_view(p).device, dtype=torch.float32, copy=True)
         for p, state in self.state.items():
             if "step" not in state:
                 continue
@@ -455,6 +500,42 @@ class FusedAdamW(torch.optim.Optimizer):
             elif isinstance(step, torch.Tensor):
                 state["step"] = int(step.item())
 
+    def _stream_ids(self) -> Dict[torch.Tensor, int]:
+        """Every parameter's index in the flattened ``param_groups`` order, the
+        number ``state_dict()`` knows it by: its stream of random bits."""
+        flat = (p for g in self.param_groups for p in g["params"])
+        return {p: i for i, p in enumerate(flat)}
+
+    def _rounding_args(self, masters, stream_ids) -> dict:
+        """The trailing arguments of ``adamw_step`` / ``adamw_clip_step``."""
+        if self.rounding == "master":
+            return dict(rounding=2, masters=masters)
+        if self.rounding == "stochastic":
+            return dict(rounding=1, stream_ids=stream_ids)
+        return {}
+
+    def _start32(self, p: torch.Tensor, state: dict) -> torch.Tensor:
+        """torch path: the fp32 value the step starts from. In master mode the
+        master copy wherever its rounding still has the bits of ``p``, else
+        ``p``, which someone has written since."""
+        pf = p.float()
+        if self.rounding != "master":
+            return pf
+        as_int = {2: torch.int16, 4: torch.int32, 8: torch.int64}[p.element_size()]
+        ours = state["master"].to(p.dtype).view(as_int) == p.view(as_int)
+        return torch.where(ours, state["master"], pf)
+
+    def _rounded(self, p: torch.Tensor, p_new: torch.Tensor, seed: int, step: int,
+                 stream_id: int) -> torch.Tensor:
+        """torch path: fp32 ``p_new`` as ``p`` stores it."""
+        if self.rounding == "stochastic" and p.dtype == torch.bfloat16:
+            from torchft_amd.ops.adamw_ref import sr_bits, stochastic_round_bf16
+
+            r16 = sr_bits(p.numel(), seed=seed, step=step, stream_id=stream_id)
+            flat = stochastic_round_bf16(p_new.reshape(-1), r16.to(p.device))
+            return flat.view_as(p)
+        return p_new.to(p.dtype)
+
     @torch.no_grad()
     def _step_clip(self) -> None:
         params: List[torch.Tensor] = []
@@ -462,6 +543,9 @@ class FusedAdamW(torch.optim.Optimizer):
         exp_avgs: List[torch.Tensor] = []
         exp_avg_sqs: List[torch.Tensor] = []
         steps: List[torch.Tensor] = []
+        masters: List[torch.Tensor] = []
+        stream_ids: List[int] = []
+        all_ids = self._stream_ids() if self.rounding == "stochastic" else {}
         groups = []
         for group in self.param_groups:
             n0 = len(params)
@@ -476,6 +560,12 @@ class FusedAdamW(torch.optim.Optimizer):
                     state["step"] = torch.zeros((), dtype=torch.int32, device=p_loc.device)
                     state["exp_avg"] = torch.zeros_like(p_loc, dtype=torch.float32)
                     state["exp_avg_sq"] = torch.zeros_like(p_loc, dtype=torch.float32)
+                if self.rounding == "master":
+                    if "master" not in state:
+                        state["master"] = p_loc.float().contiguous()
+                    masters.append(state["master"])
+                elif self.rounding == "stochastic":
+                    stream_ids.append(all_ids[p])
                 params.append(p_loc)
                 grads.append(_local_view(p.grad))
                 exp_avgs.append(state["exp_avg"])
@@ -504,6 +594,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 [float(g["weight_decay"]) for g, _ in groups],
                 self.max_grad_norm, 2048, self._sumsq, self.skipped_steps,
                 self.last_grad_norm, self.norm_reduce,
+                **self._rounding_args(masters, stream_ids),
+                **({"sr_seeds": [int(g.get("sr_seed", 0)) for g, _ in groups]}
+                   if self.rounding == "stochastic" else {}),
             )
             return
 
@@ -518,9 +611,9 @@ class FusedAdamW(torch.optim.Optimizer):
         i = 0
         for group, cnt in groups:
             beta1, beta2 = group["betas"]
-            for p, g, m, v, s in zip(params[i:i + cnt], grads[i:i + cnt],
-                                     exp_avgs[i:i + cnt], exp_avg_sqs[i:i + cnt],
-                                     steps[i:i + cnt]):
+            for j, (p, g, m, v, s) in enumerate(zip(
+                    params[i:i + cnt], grads[i:i + cnt], exp_avgs[i:i + cnt],
+                    exp_avg_sqs[i:i + cnt], steps[i:i + cnt]), start=i):
                 gf = g.float() * coef
                 s1 = (s + 1).double()
                 bc1 = (1 - beta1 ** s1).float()
@@ -528,8 +621,19 @@ class FusedAdamW(torch.optim.Optimizer):
                 m_new = m * beta1 + gf * (1 - beta1)
                 v_new = v * beta2 + gf * gf * (1 - beta2)
                 denom = (v_new / bc2).sqrt_().add_(group["eps"])
-                update = (m_new / bc1) / denom + group["weight_decay"] * p.float()
-                p_new = p + (-group["lr"] * update).to(p.dtype)
+                if self.rounding == "nearest":
+                    update = (m_new / bc1) / denom + group["weight_decay"] * p.float()
+                    p_new = p + (-group["lr"] * update).to(p.dtype)
+                else:
+                    state = {"master": masters[j]} if masters else {}
+                    start = self._start32(p, state)
+                    update = (m_new / bc1) / denom + group["weight_decay"] * start
+                    new32 = start - group["lr"] * update
+                    if masters:
+                        masters[j].copy_(torch.where(finite, new32, masters[j]))
+                    # the bits need the step count on the host: this path syncs
+                    p_new = self._rounded(p, new32, int(group.get("sr_seed", 0)), int(s) + 1,
+                                          stream_ids[j] if stream_ids else 0)
                 p.copy_(torch.where(finite, p_new, p))
                 m.copy_(torch.where(finite, m_new, m))
                 v.copy_(torch.where(finite, v_new, v))
@@ -549,7 +653,9 @@ class FusedAdamW(torch.optim.Optimizer):
             # DDP) accumulate different step counts; the bias correction is
             # per step count, so bucket by it — one kernel launch per
             # distinct count (one in the common case).
-            by_step: Dict[int, List[List[torch.Tensor]]] = {}
+            by_step: Dict[int, List[list]] = {}
+            all_ids = self._stream_ids() if self.rounding == "stochastic" else {}
+            seed = int(group.get("sr_seed", 0))
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -561,29 +667,46 @@ class FusedAdamW(torch.optim.Optimizer):
                     state["exp_avg"] = torch.zeros_like(p_loc, dtype=torch.float32)
                     state["exp_avg_sq"] = torch.zeros_like(p_loc, dtype=torch.float32)
                 state["step"] += 1
-                bucket = by_step.setdefault(state["step"], [[], [], [], []])
+                bucket = by_step.setdefault(state["step"], [[], [], [], [], [], []])
                 bucket[0].append(p_loc)
                 bucket[1].append(g_loc)
                 bucket[2].append(state["exp_avg"])
                 bucket[3].append(state["exp_avg_sq"])
+                if self.rounding == "master":
+                    if "master" not in state:
+                        state["master"] = p_loc.float().contiguous()
+                    bucket[4].append(state["master"])
+                elif self.rounding == "stochastic":
+                    bucket[5].append(all_ids[p])
 
             beta1, beta2 = group["betas"]
-            for step, (params, grads, exp_avgs, exp_avg_sqs) in by_step.items():
+            for step, (params, grads, exp_avgs, exp_avg_sqs, masters, ids) in by_step.items():
                 if params[0].is_cuda and params[0].dtype == torch.bfloat16:
+                    extra = self._rounding_args(masters, ids)
+                    if self.rounding == "stochastic":
+                        extra["sr_seed"] = seed
                     hip_ext().adamw_step(
                         params, grads, exp_avgs, exp_avg_sqs, group["lr"], beta1,
-                        beta2, group["eps"], group["weight_decay"], step,
+                        beta2, group["eps"], group["weight_decay"], step, **extra,
                     )
                 else:
                     bc1 = 1 - beta1**step
                     bc2 = 1 - beta2**step
-                    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+                    for j, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
                         gf = g.float()
                         m.mul_(beta1).add_(gf, alpha=1 - beta1)
                         v.mul_(beta2).addcmul_(gf, gf, value=1 - beta2)
                         denom = (v / bc2).sqrt_().add_(group["eps"])
-                        update = (m / bc1) / denom + group["weight_decay"] * p.float()
-                        p.add_((-group["lr"] * update).to(p.dtype))
+                        if self.rounding == "nearest":
+                            update = (m / bc1) / denom + group["weight_decay"] * p.float()
+                            p.add_((-group["lr"] * update).to(p.dtype))
+                            continue
+                        start = self._start32(p, {"master": masters[j]} if masters else {})
+                        update = (m / bc1) / denom + group["weight_decay"] * start
+                        new32 = start - group["lr"] * update
+                        if masters:
+                            masters[j].copy_(new32)
+                        p.copy_(self._rounded(p, new32, seed, step, ids[j] if ids else 0))
         return None
 
 
