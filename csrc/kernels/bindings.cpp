@@ -909,17 +909,20 @@ void diloco_outer_step_fp8(const std::vector<at::Tensor>& snapshots,
 namespace {
 
 // true when a logical [B,H,S,D] tensor is a transpose view of contiguous
-// [B,S,H,D] storage (the model's projection layout)
+// [B,S,H,D] storage (the model's projection layout). A batch of one has no
+// batch stride to hold: the first rows of a longer sequence (a context-parallel
+// rank's keys) are such a view too.
 bool is_bshd(const at::Tensor& t) {
   return t.dim() == 4 && t.stride(3) == 1 && t.stride(1) == t.size(3) &&
          t.stride(2) == t.size(1) * t.size(3) &&
-         t.stride(0) == t.size(1) * t.size(2) * t.size(3);
+         (t.size(0) == 1 || t.stride(0) == t.size(1) * t.size(2) * t.size(3));
 }
 
 // The tensors of one attention call and the one rule they are held to. Every
 // logical [B,H,S,128] tensor is bf16 on the device of the first ("q"; dout for
 // fa_delta) with its batch and sequence length; its heads equal q's, or divide
-// them for k / v. Layout: if every tensor is a [B,S,H,D]-backed transpose view
+// them for k / v, which may also be longer than q (the rectangular kernels:
+// both lengths multiples of 256 then, and no document mask). Layout: if every tensor is a [B,S,H,D]-backed transpose view
 // the kernels take them as they are (bshd), otherwise each is made contiguous;
 // outputs are allocated in the layout the inputs resolved to.
 struct FaArgs {
@@ -944,13 +947,22 @@ struct FaArgs {
     push(t);
   }
 
-  // k and v: one shape, q's batch and sequence, heads dividing q's
+  // k and v: one shape, q's batch, q's sequence length or more, heads
+  // dividing q's. A k that is longer than q without v is refused as k: v
+  // agrees with q then, and k is the odd one.
   void add_kv(const at::Tensor& k, const at::Tensor& v) {
     check_kind("k", k);
     check_kind("v", v);
-    TORCH_CHECK(k.size(0) == q().size(0) && k.size(2) == q().size(2), what,
-                ": k must have q's batch and sequence length, got ", k.sizes(), " against ",
-                q().sizes());
+    const bool longer = k.size(2) > q().size(2) && v.size(2) == k.size(2);
+    TORCH_CHECK(k.size(0) == q().size(0) && (k.size(2) == q().size(2) || longer), what,
+                ": k must have q's batch and its sequence length (or, with v, a longer one), ",
+                "got ", k.sizes(), " against ", q().sizes());
+    if (k.size(2) != q().size(2)) {
+      TORCH_CHECK(q().size(2) % 256 == 0, what, ": q's sequence length ", q().size(2),
+                  " must be a multiple of 256 when k is longer (", k.size(2), ")");
+      TORCH_CHECK(k.size(2) % 256 == 0, what, ": k's sequence length ", k.size(2),
+                  " must be a multiple of 256 when it differs from q's (", q().size(2), ")");
+    }
     TORCH_CHECK(k.size(1) > 0 && q().size(1) % k.size(1) == 0,
                 "Hq must be a multiple of Hkv (k has ", k.size(1), " heads)");
     TORCH_CHECK(v.sizes() == k.sizes(), what, ": v must have k's shape, got ", v.sizes(),
@@ -976,6 +988,9 @@ struct FaArgs {
                 "doc_end are given together or not at all)");
     if (!ds.has_value()) return;
     TORCH_CHECK(causal, what, ": doc_start / doc_end need causal=True");
+    TORCH_CHECK(ts.size() < 2 || ts[1].size(2) == q().size(2), what,
+                ": doc_start / doc_end need k of q's sequence length, got ",
+                ts.size() < 2 ? 0 : ts[1].size(2), " against ", q().size(2));
     doc_start = doc("doc_start", *ds);
     doc_end = doc("doc_end", *de);
   }
@@ -1066,8 +1081,8 @@ std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
   tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
                      lse.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)k.size(1),
-                     (int)q.size(2), (float)scale, causal, a.bshd, a.doc_start_ptr(),
-                     a.doc_end_ptr(), current_stream());
+                     (int)q.size(2), (int)k.size(2), (float)scale, causal, a.bshd,
+                     a.doc_start_ptr(), a.doc_end_ptr(), current_stream());
   return {out, lse};
 }
 
@@ -1083,13 +1098,14 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
   a.check_grid();
   auto lsec = a.stat("lse", lse), deltac = a.stat("delta", delta);
   auto dq = a.out_like(0), dk = a.out_like(1), dv = a.out_like(2);
-  if (a.empty()) return {dq, dk, dv};
+  // no query rows: keys that nothing attends to have zero gradients
+  if (a.empty()) return {dq, dk.zero_(), dv.zero_()};
   auto qc = a.in(0), kc = a.in(1), vc = a.in(2), doc = a.in(3);
   tft::launch_fa_bwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), doc.data_ptr(),
                      lsec.data_ptr<float>(), deltac.data_ptr<float>(), dq.data_ptr(),
                      dk.data_ptr(), dv.data_ptr(), (int)q.size(0), (int)q.size(1),
-                     (int)k.size(1), (int)q.size(2), (float)scale, causal, a.bshd,
-                     a.doc_start_ptr(), a.doc_end_ptr(), current_stream());
+                     (int)k.size(1), (int)q.size(2), (int)k.size(2), (float)scale, causal,
+                     a.bshd, a.doc_start_ptr(), a.doc_end_ptr(), current_stream());
   return {dq, dk, dv};
 }
 

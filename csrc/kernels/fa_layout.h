@@ -1,10 +1,12 @@
 // Address math of the flash-attention kernels (flash_attn_fwd.hip,
 // flash_attn_bwd.hip): the sizes, the workgroup order, the subtiled LDS tile
 // image, the thread -> chunk staging map, the tr_b16 read offsets, the pa/pb
-// swizzle and the tile bounds of the document mask. Plain constexpr C++,
-// callable from host and device; the device-only pieces built on it are in
-// fa_tile.h. csrc/kernels/tests/fa_layout_test.cpp, fa_wg_order_test.cpp and
-// fa_doc_bounds_test.cpp check every function here on the host.
+// swizzle and the tile bounds of the document mask and of the rectangular
+// (Sq != Sk) variant. Plain constexpr C++, callable from host and device; the
+// device-only pieces built on it are in fa_tile.h.
+// csrc/kernels/tests/fa_layout_test.cpp, fa_wg_order_test.cpp,
+// fa_doc_bounds_test.cpp and fa_rect_bounds_test.cpp check every function here
+// on the host.
 #pragma once
 
 #include "kernels.h"
@@ -34,6 +36,11 @@ constexpr int kFaMaxGridY = 65535;
 // (csrc/kernels/tests/fa_wg_order_test.cpp), every (x, y) does the work it
 // always did, and results do not depend on the order blocks are dealt in:
 // this is for speed only (docs/KERNELS.md, "Workgroup order").
+// The rectangular variants (Sq rows against Sk >= Sq keys, below) keep both
+// claims. dkdv: the key blocks of the prefix all stream every query tile and
+// the ones on the diagonal shrink, so the tile counts are non-increasing from
+// x = 0. dq and the forward: block x streams off + 256 (x + 1) keys, so they
+// are non-increasing from x = nx - 1 (fa_rect_bounds_test.cpp walks both).
 // 32 bits hold n: q alone has nx * ny * 256 rows of 256 bytes, so n < 2^32
 // wherever q fits in 2^48 bytes; the largest grid the bindings could admit
 // (ny = kFaMaxGridY, S = 2^24) gives 65536 * 65535 < 2^32.
@@ -161,6 +168,30 @@ TFT_HD constexpr bool doc_qtile_skipped(int i, int de_wave_last) {
 // query lies above the first key of the wave's block jb
 TFT_HD constexpr bool doc_qtile_straddles(int ds_tile_last, int jb) {
   return ds_tile_last > jb * kFaBlk;
+}
+
+// ---- rectangular attention (Sq query rows against Sk >= Sq keys) -------------
+// Causality is aligned to the bottom-right corner: query i sees key j iff
+// j <= i + off, off = Sk - Sq. Sq and Sk are multiples of 256, so off is one
+// too and the diagonal crosses every tile where it does in the square kernels:
+// the per-element tests keep their form and only wave-uniform tile indices
+// shift by off (keys) or off / 32 (query tiles). off = 0 gives the square
+// kernels' bounds, which call these functions too.
+// (csrc/kernels/tests/fa_rect_bounds_test.cpp)
+
+// Forward and dq: one past the last key the workgroup on query rows
+// [Q0, Q0 + 256) streams. At most Sk, at least off + 256 > 0 when causal.
+TFT_HD constexpr int rect_kv_end(int Q0, int off, int Sk, bool causal) {
+  const int diag = off + Q0 + kFaWaves * kFaBlk;
+  return causal ? (Sk < diag ? Sk : diag) : Sk;
+}
+// dkdv: the first 32-query tile the workgroup on key block x (keys
+// [256 x, 256 x + 256)) streams; the range is [i_min, Sq / 32). Below Sq / 32
+// for every x < Sk / 256, since 8 x - off / 32 <= Sq / 32 - 8. x >= 0, so
+// off = 0 needs no clamp; saying so keeps the compare out of the square kernel.
+TFT_HD constexpr int rect_first_qtile(int x, int off, bool causal) {
+  const int i = x * kFaWaves - off / kFaBlk;
+  return causal ? (off == 0 || i > 0 ? i : 0) : 0;
 }
 
 // pa/pb: a wave's 32 x 64 B transpose buffer (P or dS as bf16, [row][32 keys]),

@@ -77,6 +77,13 @@ __device__ inline const int* doc_ptr(const int* first, R... rest) {
   }
 }
 
+// The RECT (Sq != Sk) variants take the key length the same way: one int in
+// the pack, and S stays the query length. RECT with DOC is not built.
+template <class... R>
+__device__ inline int rect_sk(int sk, R...) {
+  return sk;
+}
+
 // one hardware-transpose read: 4 bf16 = column (l&15), rows j=0..3 of the
 // [4][16] block at (per-lane) byte address `addr` into the LDS image
 #define TR_READ(dst, addr) \

@@ -38,6 +38,14 @@
 // per-element test runs only in tiles that straddle a boundary (bounds:
 // fa_layout.h; docs/KERNELS.md).
 //
+// Rectangular (RECT variants): Sq query rows against Sk >= Sq keys, causal
+// aligned bottom-right (key j visible to row i iff j <= i + Sk - Sq). q / dout /
+// dq / lse / delta are addressed with Sq, k / v / dk / dv with Sk. dkdv's grid
+// is the Sk / 256 key blocks and its query-tile stream starts at
+// rect_first_qtile; dq's key stream ends at rect_kv_end. The causal tests see
+// wave-uniform indices shifted by Sk - Sq, a multiple of 256, and are
+// otherwise the square kernels' (fa_layout.h; docs/KERNELS.md).
+//
 // MFMA lane mappings (verified by mfma_probe.hip on gfx950):
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
@@ -71,15 +79,22 @@ struct SmemFA {
 // DOC (both kernels): the document-mask variant (docs/KERNELS.md, "document
 // mask"). Its arrays ride in the trailing pack (fa_tile.h, doc_ptr): dkdv
 // takes doc_start and doc_end, dq doc_start alone.
-template <bool DOC, class... DocP>
+// RECT (both kernels): the rectangular variant (docs/KERNELS.md, "Rectangular
+// attention"). S is then the query length and the pack holds the key length.
+template <bool DOC, bool RECT, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     bf16* __restrict__ dk, bf16* __restrict__ dv, int B, int Hq, int Hkv,
     int S, float scale, int causal, int bshd, DocP... docp) {
-  static_assert(sizeof...(DocP) == (DOC ? 2 : 0), "DOC takes doc_start, doc_end");
+  static_assert(!(DOC && RECT), "no document mask with Sq != Sk");
+  static_assert(sizeof...(DocP) == (DOC ? 2 : RECT ? 1 : 0),
+                "DOC takes doc_start, doc_end, RECT the key length");
   __shared__ SmemFA sm;
+  int Sk = S;
+  if constexpr (RECT) Sk = rect_sk(docp...);
+  const int off = Sk - S;
   const int G = Hq / Hkv;
   // causal: block 0 streams the most query tiles; all heads of it start first
   const FaWg wg =
@@ -91,9 +106,12 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
   const int half = lane >> 5;
   const int l31 = lane & 31;
   const int jb = wg.x * kFaWaves + wave;
-  const bool active = jb * kFaBlk < S;
+  const bool active = jb * kFaBlk < Sk;
+  // RECT: the query tile whose diagonal block is the wave's key block, below
+  // 0 for the keys every row sees
+  const int jbq = jb - off / kFaBlk;
   const int nQ = S / kFaBlk;
-  const int i_min = causal ? wg.x * kFaWaves : 0;
+  const int i_min = rect_first_qtile(wg.x, off, causal);
   // DOC: the query tiles end where the document of the workgroup's last key
   // ends; a wave stops computing at doc_end of its own last key (de_w)
   int i_hi = nQ, de_w = 0;
@@ -115,7 +133,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
   unsigned char* vops = sm.v_ops[wave];
   bf16x8_vec kfrag[6];
   if (active) {
-    const int64_t kv_off = row_off(b, hkv, jb * kFaBlk + l31, Hkv, S, bshd);
+    const int64_t kv_off = row_off(b, hkv, jb * kFaBlk + l31, Hkv, Sk, bshd);
 #pragma unroll
     for (int t = 0; t < 8; t++) {
       const bf16x8_vec kv =
@@ -164,7 +182,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
     const int ds_q = ds_n;
     const bool more = t + 1 < T;  // wave-uniform
     const bool computes =
-        active && !(causal && i < jb) && !(DOC && doc_qtile_skipped(i, de_w));
+        active && !(causal && i < jbq) && !(DOC && doc_qtile_skipped(i, de_w));
 
     // phase 1: S^T, dP^T, then P / dS into the wave's pa / pb
     if (computes) {
@@ -191,7 +209,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
       unsigned char* pb = sm.pb[wave];
       // q row minus the lane's first key row: the causal test of C register
       // rg is one compare against the constant c_row(rg, 0)
-      const int qk = (i - jb) * kFaBlk + l31 - 4 * half;
+      const int qk = (i - jbq) * kFaBlk + l31 - 4 * half;
       // DOC: only a tile that straddles a boundary (wave-uniform test) has
       // keys below doc_start of its queries. Their scores become -inf there,
       // so the loop below, unchanged, gives them P = exp(-inf) = 0 and dS = 0.
@@ -295,7 +313,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dkdv_kernel(
 #pragma unroll
     for (int rg = 0; rg < 16; rg++) {
       const int key = c_row(rg, half);
-      const int64_t row = row_off(b, hkv, jb * kFaBlk + key, Hkv, S, bshd);
+      const int64_t row = row_off(b, hkv, jb * kFaBlk + key, Hkv, Sk, bshd);
       const int d = dt * 32 + l31;
       dk[row + d] = __float2bfloat16(dk_acc[dt][rg]);
       dv[row + d] = __float2bfloat16(dv_acc[dt][rg]);
@@ -318,15 +336,20 @@ struct SmemDqDoc : SmemDq {
 };
 
 // ---- kernel 2: dQ ---------------------------------------------------------
-template <bool DOC, class... DocP>
+template <bool DOC, bool RECT, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ delta,
     bf16* __restrict__ dq, int B, int Hq, int Hkv, int S, float scale,
     int causal, int bshd, DocP... docp) {
-  static_assert(sizeof...(DocP) == (DOC ? 1 : 0), "DOC takes doc_start");
+  static_assert(!(DOC && RECT), "no document mask with Sq != Sk");
+  static_assert(sizeof...(DocP) == (DOC || RECT ? 1 : 0),
+                "DOC takes doc_start, RECT the key length");
   __shared__ std::conditional_t<DOC, SmemDqDoc, SmemDq> sm;
+  int Sk = S;
+  if constexpr (RECT) Sk = rect_sk(docp...);
+  const int off = Sk - S;
   const int G = Hq / Hkv;
   // causal: the last q block streams the most key tiles; all heads of it
   // start first
@@ -342,9 +365,9 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
   const int bx = wg.x;
   const int ib = bx * kFaWaves + wave;
   const bool active = ib * kFaBlk < S;
-  const int nK64 = (S + 63) / 64;
-  const int kv_hi = causal ? (bx * kFaWaves + kFaWaves) * kFaBlk : S;
-  const int T = causal ? (min(kv_hi, S) + 63) / 64 : nK64;
+  // RECT: the key at the diagonal of the wave's first row
+  const int ik0 = ib * kFaBlk + off;
+  const int T = (rect_kv_end(bx * kFaWaves * kFaBlk, off, Sk, causal) + 63) / 64;
 
   bf16x8_vec qfrag[8], dofrag[8];
   float lse_row[16], delta_row[16];
@@ -386,8 +409,8 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
   const unsigned tr_off = Tile<64>::tr_lane_off(lane);
 
   auto tile_regs = [&](int j) -> TileRegs<64> {
-    const int64_t off = row_off(b, hkv, j * 64, Hkv, S, bshd);
-    return load_tiles<64>(k + off, v + off, kv_ld);
+    const int64_t at = row_off(b, hkv, j * 64, Hkv, Sk, bshd);
+    return load_tiles<64>(k + at, v + at, kv_ld);
   };
 
   // prologue: stage key tile 0 (DOC: the first tile needed)
@@ -402,7 +425,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     const bool more = j + 1 < T;
     if (more) pre = tile_regs(j + 1);
 
-    if (active && !(causal && j * 64 > ib * kFaBlk + kFaBlk - 1) &&
+    if (active && !(causal && j * 64 > ik0 + kFaBlk - 1) &&
         !(DOC && doc_block_skipped(j * 64 + 32, ds_w0))) {
       const unsigned char* kimg = sm.k_img[cur].sub;
       const unsigned char* vimg = sm.v_img[cur].sub;
@@ -412,7 +435,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
 #pragma unroll
       for (int s = 0; s < 2; s++) {  // two 32-key halves per staged tile
         const int kb0 = j * 64 + s * 32;
-        if (causal && kb0 > ib * kFaBlk + kFaBlk - 1) break;
+        if (causal && kb0 > ik0 + kFaBlk - 1) break;
         if (DOC && doc_block_skipped(kb0, ds_w0)) continue;
 
         f32x16 s_acc = {};
@@ -428,7 +451,7 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
         const int kg = kb0 + l31;
         // key minus the lane's first q row: the causal test of C register
         // rg is one compare against the constant c_row(rg, 0)
-        const int kq = kg - ib * kFaBlk - 4 * half;
+        const int kq = kg - ik0 - 4 * half;
         // DOC: only a block that straddles a boundary (wave-uniform test) has
         // keys below doc_start of some row. Their scores become -inf there, so
         // the loop below, unchanged, gives them P = exp(-inf) = 0 and dS = 0.
@@ -550,28 +573,40 @@ void launch_fa_delta(const void* dout, const void* o, float* delta,
 
 void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout,
                    const float* lse, const float* delta, void* dq, void* dk,
-                   void* dv, int B, int Hq, int Hkv, int S, float scale,
+                   void* dv, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
                    hipStream_t stream) {
   const int nblk = (S + kFaBlk * kFaWaves - 1) / (kFaBlk * kFaWaves);
+  if (Sk != S) {  // dkdv's grid is over the key blocks, dq's over the query blocks
+    hipLaunchKernelGGL((fa_bwd_dkdv_kernel<false, true, int>),
+                       dim3(Sk / (kFaBlk * kFaWaves), B * Hkv), dim3(kFaThreads), 0, stream,
+                       (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout,
+                       lse, delta, (bf16*)dk, (bf16*)dv, B, Hq, Hkv, S, scale,
+                       causal ? 1 : 0, bshd ? 1 : 0, Sk);
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, true, int>), dim3(nblk, B * Hq),
+                       dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq,
+                       Hkv, S, scale, causal ? 1 : 0, bshd ? 1 : 0, Sk);
+    return;
+  }
   if (doc_start != nullptr && doc_end != nullptr) {
-    hipLaunchKernelGGL((fa_bwd_dkdv_kernel<true, const int*, const int*>),
+    hipLaunchKernelGGL((fa_bwd_dkdv_kernel<true, false, const int*, const int*>),
                        dim3(nblk, B * Hkv), dim3(kFaThreads), 0, stream, (const bf16*)q,
                        (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta,
                        (bf16*)dk, (bf16*)dv, B, Hq, Hkv, S, scale, 1, bshd ? 1 : 0,
                        doc_start, doc_end);
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, const int*>), dim3(nblk, B * Hq),
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, false, const int*>), dim3(nblk, B * Hq),
                        dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq,
                        Hkv, S, scale, 1, bshd ? 1 : 0, doc_start);
     return;
   }
-  hipLaunchKernelGGL(fa_bwd_dkdv_kernel<false>, dim3(nblk, B * Hkv), dim3(kFaThreads), 0,
-                     stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
+  hipLaunchKernelGGL((fa_bwd_dkdv_kernel<false, false>), dim3(nblk, B * Hkv),
+                     dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, B, Hq,
                      Hkv, S, scale, causal ? 1 : 0, bshd ? 1 : 0);
-  hipLaunchKernelGGL(fa_bwd_dq_kernel<false>, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
-                     stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
+  hipLaunchKernelGGL((fa_bwd_dq_kernel<false, false>), dim3(nblk, B * Hq),
+                     dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq, Hkv, S,
                      scale, causal ? 1 : 0, bshd ? 1 : 0);
 }

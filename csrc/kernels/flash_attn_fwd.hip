@@ -32,6 +32,13 @@
 //   streamed or computed; the per-element test runs only in blocks that
 //   straddle a boundary (bounds: fa_layout.h; docs/KERNELS.md).
 //
+//   Rectangular (RECT variant): Sq query rows against Sk >= Sq keys, the
+//   causal diagonal aligned bottom-right (key j visible to row i iff
+//   j <= i + Sk - Sq): a context-parallel rank's shard against the keys up to
+//   its own. q / out / lse are addressed with Sq, k / v with Sk, and the key
+//   positions the causal tests see are shifted down by Sk - Sq, a multiple of
+//   256: wave-uniform, so the diagonal tiles run the square kernel's code.
+//
 // MFMA lane mappings (mfma_probe.hip):
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
@@ -98,14 +105,23 @@ __device__ inline float half_combine_sum(float v) {
 // DOC: the document-mask variant (docs/KERNELS.md, "document mask"). Its one
 // extra argument, doc_start (int32 [B,S]), rides in the trailing pack so that
 // the plain instantiation keeps its parameter list and its code.
-template <bool DOC, class... DocP>
+// RECT: the rectangular variant (docs/KERNELS.md, "Rectangular attention").
+// S is then the query length and the pack holds the key length.
+template <bool DOC, bool RECT, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, bf16* __restrict__ out,
     float* __restrict__ lse, int B, int Hq, int Hkv, int S, float scale,
     int causal, int bshd, DocP... docp) {
-  static_assert(sizeof...(DocP) == (DOC ? 1 : 0), "DOC takes doc_start");
+  static_assert(!(DOC && RECT), "no document mask with Sq != Sk");
+  static_assert(sizeof...(DocP) == (DOC || RECT ? 1 : 0),
+                "DOC takes doc_start, RECT the key length");
   __shared__ SmemFwd sm;
+  // keys: Sk of them, and key j sits at j - off on the causal diagonal of the
+  // query rows
+  int Sk = S;
+  if constexpr (RECT) Sk = rect_sk(docp...);
+  const int off = Sk - S;
   const int G = Hq / Hkv;
   // causal: the last q block streams the most key tiles; all heads of it
   // start first
@@ -136,12 +152,12 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
     }
   }
 
-  const bf16* k_base = k + row_off(b, hkv, 0, Hkv, S, bshd);
-  const bf16* v_base = v + row_off(b, hkv, 0, Hkv, S, bshd);
+  const bf16* k_base = k + row_off(b, hkv, 0, Hkv, Sk, bshd);
+  const bf16* v_base = v + row_off(b, hkv, 0, Hkv, Sk, bshd);
   const int64_t kv_ld = bshd ? (int64_t)Hkv * kFaD : kFaD;
 
   // number of KV tiles this WORKGROUP must stage
-  const int kv_hi = causal ? min(S, Q0 + kFaWaves * kFaBlk) : S;
+  const int kv_hi = rect_kv_end(Q0, off, Sk, causal);
   const int nT = (kv_hi + kFwdKvBlk - 1) / kFwdKvBlk;
 
   // DOC: the workgroup streams from the tile that holds doc_start of its
@@ -190,7 +206,9 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
                        v_base + (int64_t)(j + 1) * kFwdKvBlk * kv_ld, kv_ld);
     }
 
-    const int key0 = j * kFwdKvBlk;
+    // RECT: from here on the tile's keys are counted from the diagonal's
+    // origin (key off is 0), where the causal tests are the square kernel's
+    const int key0 = j * kFwdKvBlk - off;
     // this wave needs the tile only if some of its keys are visible
     if (active && (!causal || key0 <= my_q0 + kFaBlk - 1) &&
         !(DOC && doc_block_skipped(key0 + 32, ds_w0))) {
@@ -350,21 +368,28 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
 }
 
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
-                   float* lse, int B, int Hq, int Hkv, int S, float scale,
+                   float* lse, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
                    hipStream_t stream) {
   const int rows_per_wg = kFaWaves * kFaBlk;
   const int nblk = (S + rows_per_wg - 1) / rows_per_wg;
   (void)doc_end;  // the forward is query-centric: doc_start says it all
   if (doc_start != nullptr) {
-    hipLaunchKernelGGL((fa_fwd_kernel<true, const int*>), dim3(nblk, B * Hq),
+    hipLaunchKernelGGL((fa_fwd_kernel<true, false, const int*>), dim3(nblk, B * Hq),
                        dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, lse, B, Hq, Hkv, S, scale, 1,
                        bshd ? 1 : 0, doc_start);
     return;
   }
-  hipLaunchKernelGGL(fa_fwd_kernel<false>, dim3(nblk, B * Hq), dim3(kFaThreads), 0,
-                     stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
+  if (Sk != S) {  // the grid is over the query blocks
+    hipLaunchKernelGGL((fa_fwd_kernel<false, true, int>), dim3(nblk, B * Hq),
+                       dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, lse, B, Hq, Hkv, S, scale,
+                       causal ? 1 : 0, bshd ? 1 : 0, Sk);
+    return;
+  }
+  hipLaunchKernelGGL((fa_fwd_kernel<false, false>), dim3(nblk, B * Hq), dim3(kFaThreads),
+                     0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (bf16*)out, lse, B, Hq, Hkv, S, scale, causal ? 1 : 0,
                      bshd ? 1 : 0);
 }

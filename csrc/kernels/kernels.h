@@ -187,19 +187,24 @@ void launch_outer_sgd_fp8(int dtype_code, bool has_momentum, MultiTensorTable tb
 // [B,S,H,128] (fa_layout.h, row_off). lse: dense fp32 [B,Hq,S]. S % 256 == 0.
 // doc_start / doc_end: the document mask (fa_layout.h), dense int32 [B,S]
 // device arrays, both null for no mask and given only with causal.
+// Sk: the key length, k / v being [B,Hkv,Sk,128]. Sk == S is the square
+// kernel. Sk > S is the rectangular one (fa_layout.h): both multiples of 256,
+// the causal diagonal aligned bottom-right, no document mask; q / out / lse
+// keep the query length S.
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
-                   float* lse, int B, int Hq, int Hkv, int S, float scale,
+                   float* lse, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
                    tft_stream stream);
 
 // flash_attn_bwd.hip --------------------------------------------------------
 // tensors and layouts as in the forward; delta: dense fp32 [B,Hq,S], the row
-// sums of dout * o. launch_fa_bwd needs S % 128 == 0.
+// sums of dout * o. launch_fa_bwd needs S % 128 == 0; with Sk > S, as in the
+// forward, dq has q's shape and dk / dv have k's.
 void launch_fa_delta(const void* dout, const void* o, float* delta,
                      int64_t rows, int Hq, int S, bool bshd, tft_stream stream);
 void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout,
                    const float* lse, const float* delta, void* dq, void* dk,
-                   void* dv, int B, int Hq, int Hkv, int S, float scale,
+                   void* dv, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
                    tft_stream stream);
 

@@ -5,12 +5,23 @@ The world-1 path is plain flash; the world>1 merge path is exercised by
 pinning prefix_len explicitly. Measures fwd+bwd ms and peak memory —
 the point of the flash merge is that 128k contexts run at flash memory
 (the round-1 fp32-scores version OOMed by construction).
+
+--rect: what one rank computes after the all-gather (cp_rank_attention), the
+merge path against the rectangular kernels (TORCHFT_AMD_CP_RECT), both in one
+process and alternated inside every round, forward + backward between device
+events, ms as median [min-max] over the rounds. Default shape: the last rank
+of a world-4 split of the bench shape (B=1, Hq=32, Hkv=8, s=2048, Sk=8192).
+The two paths' outputs and gradients are compared first. Run on a GPU host.
+
+    python scripts/bench_cp.py --rect [--shape B,Hq,Hkv,s] [--world W] [--rank R]
 """
+import argparse
 import os, sys, time
+import statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from torchft_amd.parallel.cp import _MergedFlashAttn
+from torchft_amd.parallel.cp import _MergedFlashAttn, cp_rank_attention
 
 def bench(S_local, prefix, iters=5):
     B, Hq, Hkv, D = 1, 32, 8, 128
@@ -35,6 +46,66 @@ def bench(S_local, prefix, iters=5):
     print(f"S_local={S_local} prefix={prefix} (ctx={prefix+S_local}): "
           f"{ms:8.2f} ms fwd+bwd, peak {peak:.1f} GiB", flush=True)
 
+
+def bench_rect(B, Hq, Hkv, s, world, rank, rounds, iters):
+    """merge (rect=False) against rect (rect=True) on the shards a model
+    hands cp_attention: [B, s, H, D], K / V gathered to [B, world*s, Hkv, D]."""
+    assert torch.cuda.is_available(), "a measurement needs the GPU"
+    gen = torch.Generator(device="cuda").manual_seed(0)
+
+    def mk(S, H, grad=True):
+        t = torch.randn(B, S, H, 128, device="cuda", dtype=torch.bfloat16, generator=gen)
+        return t.requires_grad_(grad)
+
+    q, k, v, g = mk(s, Hq), mk(world * s, Hkv), mk(world * s, Hkv), mk(s, Hq, False)
+
+    def step(rect, keep=False):
+        out = cp_rank_attention(q, k, v, rank, world, True, rect)
+        out.backward(g)
+        res = (out.detach(), q.grad, k.grad, v.grad) if keep else None
+        q.grad = k.grad = v.grad = None
+        return res
+
+    paths = {"merge": False, "rect": True}
+    a, b = step(False, keep=True), step(True, keep=True)
+    for name, x, y in zip(("out", "dq", "dk", "dv"), a, b):
+        print(f"{name}: max |merge - rect| = {(x.float() - y.float()).abs().max().item():.3e}"
+              f" (max |merge| {x.float().abs().max().item():.3e})", flush=True)
+    for rect in paths.values():  # warm up
+        for _ in range(3):
+            step(rect)
+    torch.cuda.synchronize()
+    times = {n: [] for n in paths}
+    for rnd in range(rounds):
+        for n, rect in paths.items():
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            for _ in range(iters):
+                step(rect)
+            e1.record()
+            torch.cuda.synchronize()
+            times[n].append(e0.elapsed_time(e1) / iters)
+        print(f"round {rnd}: " + "  ".join(f"{n} {t[-1]:.3f}" for n, t in times.items()),
+              flush=True)
+    for n, t in times.items():
+        print(f"{n}: fwd+bwd {statistics.median(t):.3f} ms [{min(t):.3f}-{max(t):.3f}] over "
+              f"{rounds} rounds x {iters}, B={B} Hq={Hq} Hkv={Hkv} s={s} Sk={(rank + 1) * s} "
+              f"(rank {rank} of {world})")
+
+
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rect", action="store_true",
+                    help="merge path against the rectangular kernels at one rank's shape")
+    ap.add_argument("--shape", default="1,32,8,2048", help="B,Hq,Hkv,s (with --rect)")
+    ap.add_argument("--world", type=int, default=4)
+    ap.add_argument("--rank", type=int, default=-1, help="default: the last rank")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=50)
+    a = ap.parse_args()
+    if a.rect:
+        bench_rect(*(int(x) for x in a.shape.split(",")), a.world,
+                   a.rank % a.world, a.rounds, a.iters)
+        sys.exit(0)
     for S_local, prefix in [(16384, 16384), (32768, 32768), (65536, 65536)]:
         bench(S_local, prefix)

@@ -33,10 +33,13 @@ import torch
 
 from torchft_amd.ops import hip_ext
 
-# launch_fa_bwd as it is now (two document-mask arrays before the stream,
-# passed as null here) and as it was before the document mask
+# launch_fa_bwd as it is now (the key length after S, given as S here; two
+# document-mask arrays before the stream, passed as null), as it was before
+# the rectangular kernels and as it was before the document mask
 _SYM = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
-        "iiiifbbPKiS6_P12ihipStream_t")
+        "iiiiifbbPKiS6_P12ihipStream_t")
+_SYM_NO_SK = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
+              "iiiifbbPKiS6_P12ihipStream_t")
 _SYM_NO_DOC = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
                "iiiifbbP12ihipStream_t")
 D = 128
@@ -46,10 +49,12 @@ class Build:
     def __init__(self, spec):
         self.name, path = spec.split("=", 1)
         lib = ctypes.CDLL(os.path.abspath(path))
-        self.doc_args = hasattr(lib, _SYM)
-        self.fn = getattr(lib, _SYM if self.doc_args else _SYM_NO_DOC)
+        self.sk_arg = hasattr(lib, _SYM)
+        self.doc_args = self.sk_arg or hasattr(lib, _SYM_NO_SK)
+        self.fn = getattr(lib, _SYM if self.sk_arg else
+                          _SYM_NO_SK if self.doc_args else _SYM_NO_DOC)
         self.fn.restype = None
-        self.fn.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 4 + [
+        self.fn.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * (5 if self.sk_arg else 4) + [
             ctypes.c_float, ctypes.c_bool, ctypes.c_bool] + [
             ctypes.c_void_p] * (3 if self.doc_args else 1)
 
@@ -58,7 +63,8 @@ class Build:
         self.fn(p["q"].data_ptr(), p["k"].data_ptr(), p["v"].data_ptr(),
                 p["dout"].data_ptr(), p["lse"].data_ptr(), p["delta"].data_ptr(),
                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                B, Hq, p["k"].shape[1], S, D ** -0.5, p["causal"], p["bshd"],
+                B, Hq, p["k"].shape[1], S, *((S,) if self.sk_arg else ()),
+                D ** -0.5, p["causal"], p["bshd"],
                 *((None, None) if self.doc_args else ()),
                 torch.cuda.current_stream().cuda_stream)
 

@@ -22,9 +22,14 @@ gives. The tile counts are restated from the kernels:
         (flash_attn_bwd.hip, `T` / `j0`; doc_first_tile in fa_layout.h)
   fwd   as dq (flash_attn_fwd.hip, `nT` / `j0`)
 
+With --sk the launches are the rectangular ones (S query rows against Sk >= S
+keys, off = Sk - S; rect_first_qtile / rect_kv_end in fa_layout.h): dkdv has
+Sk / 256 blocks of G * (S / 32 - max(0, 8 x - off / 32)) tiles, dq and the
+forward S / 256 blocks of (off + 256 (x + 1)) / 64.
+
 A model, not a measurement: docs/KERNELS.md, "Workgroup order", has both.
 
-    python scripts/fa_wg_order_model.py [--shape B,Hq,Hkv,S] [--docs N]
+    python scripts/fa_wg_order_model.py [--shape B,Hq,Hkv,S] [--docs N] [--sk Sk]
 """
 import argparse
 import heapq
@@ -32,9 +37,14 @@ import heapq
 CUS, XCDS = 256, 8
 
 
-def tiles(kernel, x, G, S, doc_len):
+def tiles(kernel, x, G, S, doc_len, off=0):
     """Tiles block x streams; doc_len = None is plain causal, otherwise the
-    row is packed with equal documents of doc_len tokens (a multiple of 256)."""
+    row is packed with equal documents of doc_len tokens (a multiple of 256).
+    off > 0 (no documents): S query rows against S + off keys."""
+    if off:
+        if kernel == "dkdv":
+            return G * (S // 32 - max(0, 8 * x - off // 32))
+        return (off + (x + 1) * 256) // 64
     if kernel == "dkdv":
         last_key = min((x + 1) * 256, S) - 1
         end = S if doc_len is None else (last_key // doc_len + 1) * doc_len
@@ -73,15 +83,15 @@ def makespan(costs, model):
     return worst
 
 
-def ratio(kernel, order, model, B, Hq, Hkv, S, doc_len):
-    nx = (S + 255) // 256
+def ratio(kernel, order, model, B, Hq, Hkv, S, doc_len, off=0):
+    nx = ((S + off if kernel == "dkdv" else S) + 255) // 256
     ny = B * (Hkv if kernel == "dkdv" else Hq)
     G = Hq // Hkv if kernel == "dkdv" else 1
     costs, seen = [], set()
     for n in range(nx * ny):
         x, y = order(kernel, n, nx, ny)
         seen.add((x, y))
-        costs.append(tiles(kernel, x, G, S, doc_len))
+        costs.append(tiles(kernel, x, G, S, doc_len, off))
     assert len(seen) == nx * ny, "the order is not a bijection of the grid"
     return makespan(costs, model) / (sum(costs) / CUS), sum(costs)
 
@@ -91,8 +101,18 @@ def main():
     ap.add_argument("--shape", default="4,32,8,8192", help="B,Hq,Hkv,S")
     ap.add_argument("--docs", type=int, default=8,
                     help="equal documents per row of the document-mask lines")
+    ap.add_argument("--sk", type=int, default=0,
+                    help="key length of the rectangular launches (S is then the query length)")
     a = ap.parse_args()
     B, Hq, Hkv, S = (int(v) for v in a.shape.split(","))
+    if a.sk:
+        assert a.sk >= S and a.sk % 256 == 0 and S % 256 == 0, "Sk >= S, multiples of 256"
+        print(f"B={B} Hq={Hq} Hkv={Hkv} Sq={S} Sk={a.sk}: makespan / ideal on {CUS} CUs")
+        print(f"{'launch':<22}{'tiles':>9}  {'ranked A':>9} {'ranked B':>9}")
+        for kernel in ("dkdv", "dq", "fwd"):
+            r = [ratio(kernel, rank_major_order, m, B, Hq, Hkv, S, None, a.sk - S) for m in "AB"]
+            print(f"{kernel + ' rect':<22}{r[0][1]:>9}  {r[0][0]:>9.2f} {r[1][0]:>9.2f}")
+        return
     assert S % (256 * a.docs) == 0, "documents of a multiple of 256 tokens"
     print(f"B={B} Hq={Hq} Hkv={Hkv} S={S}: makespan / ideal on {CUS} CUs")
     print(f"{'launch':<22}{'tiles':>9}  {'present A':>9} {'present B':>9}"

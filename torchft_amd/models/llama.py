@@ -52,11 +52,14 @@ def fused_qkv_rope_enabled() -> bool:
 @dataclass
 class CPPlan:
     """Context-parallel plan: this rank holds sequence shard ``rank`` of
-    ``world``; attention all-gathers KV over ``pg`` (parallel/cp.py)."""
+    ``world``; attention all-gathers KV over ``pg`` (parallel/cp.py).
+    ``rect``: run the rectangular attention kernels on the gathered keys where
+    they apply; None reads TORCHFT_AMD_CP_RECT (off by default)."""
 
     pg: object  # torchft_amd.process_group.ProcessGroup
     rank: int
     world: int
+    rect: Optional[bool] = None
 
 
 @dataclass
@@ -146,7 +149,8 @@ class Attention(nn.Module):
             from torchft_amd.parallel.cp import cp_attention
 
             out = cp_attention(
-                q, k, v, self.cp.pg, self.cp.rank, self.cp.world, causal=True
+                q, k, v, self.cp.pg, self.cp.rank, self.cp.world, causal=True,
+                rect=self.cp.rect,
             )
             return self.wo(out.reshape(B, S, -1))
         # SDPA layout [B, H, S, D]; custom CDNA4 backward where enabled

@@ -726,4 +726,8 @@ from torchft_amd.ops.diloco import (  # noqa: E402,F401
 
 # ----------------------------------------------------------------- Flash attention
 
-from torchft_amd.ops.flash_attention import DocMask, flash_attention  # noqa: E402,F401
+from torchft_amd.ops.flash_attention import (  # noqa: E402,F401
+    DocMask,
+    flash_attention,
+    flash_attention_rect,
+)

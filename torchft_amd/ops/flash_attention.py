@@ -20,6 +20,13 @@ hand-written forward always runs, whatever TORCHFT_AMD_CUSTOM_FA_FWD says:
 aten's flash forward takes no mask. docs/KERNELS.md, "document mask".
 ``DocMask.positions()`` gives the position of every token inside its document,
 for ``ops.qkv_rope`` to restart the rotary positions at document starts.
+
+Rectangular attention: ``flash_attention_rect(q, k, v)`` takes Sq query rows
+against Sk >= Sq keys with the causal diagonal aligned bottom-right (row i sees
+key j iff j <= i + Sk - Sq), which is what a context-parallel rank computes.
+Both lengths are multiples of 256 on the kernel path, and the hand-written
+forward always runs there: the backward needs its logsumexp under exactly this
+mask. docs/KERNELS.md, "Rectangular attention".
 """
 
 from __future__ import annotations
@@ -152,7 +159,9 @@ class _FlashAttentionFn(torch.autograd.Function):
             ctx.causal = causal
             ctx.scale = scale
             return out
-        if custom_fa_fwd_enabled() and q.shape[2] % 256 == 0:
+        # unequal lengths (flash_attention_rect): aten's causal forward aligns
+        # the diagonal top-left, so its lse is another mask's
+        if q.shape[2] != k.shape[2] or (custom_fa_fwd_enabled() and q.shape[2] % 256 == 0):
             out, lse = hip_ext().fa_fwd(q, k, v, scale, causal)
         else:
             out, lse, *_ = torch.ops.aten._scaled_dot_product_flash_attention(
@@ -227,4 +236,53 @@ def flash_attention(
         return _FlashAttentionFn.apply(q, k, v, causal, scale)
     return F.scaled_dot_product_attention(
         q, k, v, is_causal=causal, scale=scale, enable_gqa=q.shape[1] != k.shape[1]
+    )
+
+
+def _rect_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """``_supported`` with the rectangular kernels' length rule in place of
+    equal lengths: k at least as long as q, both multiples of 256."""
+    return (
+        q.is_cuda
+        and q.dtype == torch.bfloat16
+        and q.shape[-1] == 128
+        and q.shape[2] % 256 == 0
+        and k.shape[2] % 256 == 0
+        and k.shape[2] >= q.shape[2]
+        and q.shape[1] % k.shape[1] == 0
+        and custom_fa_enabled()
+        and hip_ext() is not None
+    )
+
+
+def flash_attention_rect(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    causal: bool = True,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Attention of Sq query rows against Sk >= Sq keys ([B, H, S, D] layout,
+    GQA-native), the causal diagonal aligned to the bottom-right corner: query
+    ``i`` sees key ``j`` iff ``j <= i + (Sk - Sq)``. The rows are the last Sq
+    positions of the key range, as on a context-parallel rank.
+
+    Where the kernels apply (a HIP device, bf16, D = 128, both lengths
+    multiples of 256, heads dividing, TORCHFT_AMD_CUSTOM_FA not 0, the
+    extension built) this is one hand-written forward launch and, in the
+    backward, delta + dkdv + dq (equal lengths are ``flash_attention``'s
+    square case and take its forward). Everywhere else stock SDPA runs with
+    an explicit [Sq, Sk] boolean mask."""
+    if k.shape[2] < q.shape[2]:
+        raise ValueError(f"k has {k.shape[2]} positions, fewer than q's {q.shape[2]}")
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    if _rect_supported(q, k):
+        return _FlashAttentionFn.apply(q, k, v, causal, scale)
+    mask = None
+    if causal:
+        Sq, Sk = q.shape[2], k.shape[2]
+        mask = torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).tril_(Sk - Sq)
+    return F.scaled_dot_product_attention(
+        q, k, v, attn_mask=mask, scale=scale, enable_gqa=q.shape[1] != k.shape[1]
     )

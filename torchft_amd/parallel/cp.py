@@ -19,17 +19,32 @@ the cost of 2(W-1) p2p hops per layer and is the planned upgrade for
 
 Backward: dK/dV are computed for the full context on every rank and
 reduce-scattered (sum) back to the owning shard.
+
+What a rank computes after the gather is :func:`cp_rank_attention`. By default
+that is the flash + LSE merge below (``_MergedFlashAttn``); with
+``TORCHFT_AMD_CP_RECT=1`` (or ``CPPlan(rect=True)``) it is one
+``ops.flash_attention_rect`` call on the keys up to the rank's own: the
+hand-written rectangular kernels (docs/KERNELS.md, "Rectangular attention").
 """
 
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 from torch.distributed.distributed_c10d import AllgatherOptions, AllreduceOptions, ReduceOp
 
+from torchft_amd.ops.flash_attention import _rect_supported, flash_attention_rect
 from torchft_amd.process_group import ProcessGroup
+
+_ENV_RECT = "TORCHFT_AMD_CP_RECT"
+
+
+def cp_rect_enabled() -> bool:
+    """The rectangular attention kernels under CP (opt-in)."""
+    return os.environ.get(_ENV_RECT, "0") in ("1", "true", "True")
 
 
 def shard_sequence(t: torch.Tensor, rank: int, world: int, dim: int = 1) -> torch.Tensor:
@@ -84,6 +99,7 @@ def cp_attention(
     rank: int,
     world: int,
     causal: bool = True,
+    rect: Optional[bool] = None,
 ) -> torch.Tensor:
     """Context-parallel attention.
 
@@ -91,6 +107,8 @@ def cp_attention(
         q/k/v: this rank's sequence shard, [B, s, H, D] ([B, s, Hkv, D] for
             k/v with GQA), shard ``rank`` of ``world``.
         pg: the CP process group (None or world==1 -> plain attention).
+        rect: run the rectangular kernels where they apply
+            (:func:`cp_rank_attention`); None reads TORCHFT_AMD_CP_RECT.
     Returns:
         attention output for this rank's Q shard, [B, s, H, D].
     """
@@ -104,6 +122,37 @@ def cp_attention(
 
     k_full = _AllGatherSeq.apply(k, pg, rank, world)
     v_full = _AllGatherSeq.apply(v, pg, rank, world)
+    return cp_rank_attention(q, k_full, v_full, rank, world, causal, rect)
+
+
+def cp_rank_attention(
+    q: torch.Tensor,
+    k_full: torch.Tensor,
+    v_full: torch.Tensor,
+    rank: int,
+    world: int,
+    causal: bool = True,
+    rect: Optional[bool] = None,
+) -> torch.Tensor:
+    """What rank ``rank`` of ``world`` computes once K / V are gathered: its
+    query shard q [B, s, H, D] against k_full / v_full [B, world*s, Hkv, D].
+    No communication; the gradients of k_full / v_full cover the full context.
+
+    ``rect`` (None: TORCHFT_AMD_CP_RECT): where the rectangular kernels apply,
+    one ``flash_attention_rect`` call on the keys the shard can see, the first
+    ``rank*s + s`` (all of them when not causal). The keys past them get their
+    zero gradient from autograd's narrow. For B > 1 that key view is not one
+    dense [B, S, H, D] block and the binding copies the call to contiguous
+    [B, H, S, D] (docs/ROADMAP.md). Otherwise, and wherever the kernels do not
+    apply, the flash + LSE merge runs."""
+    s = q.shape[1]
+    if cp_rect_enabled() if rect is None else rect:
+        n = rank * s + s if causal else k_full.shape[1]
+        qT = q.transpose(1, 2)
+        kT = k_full[:, :n].transpose(1, 2)
+        vT = v_full[:, :n].transpose(1, 2)
+        if _rect_supported(qT, kT):
+            return flash_attention_rect(qT, kT, vT, causal=causal).transpose(1, 2)
 
     if not causal:
         out = F.scaled_dot_product_attention(
