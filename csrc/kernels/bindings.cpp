@@ -601,6 +601,32 @@ struct RoundingArgs {
   }
 };
 
+// The columns of an update table (kernels.h, AdamwLaunch): the four of every
+// mode, the device step counts where given (clip mode), the rounding mode's own
+std::vector<Column> adamw_columns(const TensorList& params, const TensorList& grads,
+                                  const TensorList& exp_avgs, const TensorList& exp_avg_sqs,
+                                  const TensorList* steps, const RoundingArgs& ra) {
+  std::vector<Column> cols = {{&params, at::kBFloat16},
+                              {&grads, at::kBFloat16},
+                              {&exp_avgs, at::kFloat},
+                              {&exp_avg_sqs, at::kFloat}};
+  if (steps) cols.push_back({steps, at::kInt, /*one_element=*/true});
+  ra.add_column(cols);
+  return cols;
+}
+
+// One update launch: `a` brings the table and what its mode reads, the rest is
+// one param group's hyper-parameters
+void launch_adamw_update(tft::AdamwLaunch a, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, tft_stream stream) {
+  a.lr = (float)lr;
+  a.beta1 = (float)beta1;
+  a.beta2 = (float)beta2;
+  a.eps = (float)eps;
+  a.weight_decay = (float)weight_decay;
+  tft::launch_adamw(a, stream);
+}
+
 }  // namespace
 
 void adamw_step(const std::vector<at::Tensor>& params,
@@ -613,44 +639,21 @@ void adamw_step(const std::vector<at::Tensor>& params,
   TORCH_CHECK(!params.empty(), "adamw_step: need at least one tensor");
   const RoundingArgs ra("adamw_step", rounding, masters, stream_ids);
   TableSet tables(params[0], "adamw_step");
-  std::vector<Column> cols = {{&params, at::kBFloat16},
-                              {&grads, at::kBFloat16},
-                              {&exp_avgs, at::kFloat},
-                              {&exp_avg_sqs, at::kFloat}};
-  ra.add_column(cols);
-  const int h = tables.add(cols);
+  const int h =
+      tables.add(adamw_columns(params, grads, exp_avgs, exp_avg_sqs, /*steps=*/nullptr, ra));
   tables.upload();
-  const float bc1 = 1.0f - std::pow((float)beta1, (float)step);
-  const float bc2 = 1.0f - std::pow((float)beta2, (float)step);
-  if (ra.mode == tft::kRoundNearest)
-    tft::launch_adamw(tables.table(h), (float)lr, (float)beta1, (float)beta2, (float)eps,
-                      (float)weight_decay, bc1, bc2, current_stream());
-  else
-    tft::launch_adamw_rounded(ra.mode, tables.table(h), (float)lr, (float)beta1,
-                              (float)beta2, (float)eps, (float)weight_decay, bc1, bc2,
-                              RoundingArgs::key(sr_seed, step), current_stream());
+  tft::AdamwLaunch a{};
+  a.tb = tables.table(h);
+  a.rounding = ra.mode;
+  a.bc1 = 1.0f - std::pow((float)beta1, (float)step);
+  a.bc2 = 1.0f - std::pow((float)beta2, (float)step);
+  a.key = RoundingArgs::key(sr_seed, step);
+  launch_adamw_update(a, lr, beta1, beta2, eps, weight_decay, current_stream());
 }
 
 // ---- global gradient norm / clip ---------------------------------------------
 
 namespace {
-
-// One table per dtype present, all in one TableSet
-struct GradTables {
-  TensorList by_dtype[3];  // indexed by dtype_code
-  int handle[3] = {-1, -1, -1};
-};
-
-void add_grad_tables(TableSet& tables, const TensorList& tensors, GradTables& gt) {
-  for (auto& t : tensors) {
-    const int code = dtype_code(t.scalar_type());
-    TORCH_CHECK(code >= 0, "unsupported dtype for grad norm: ", t.scalar_type());
-    gt.by_dtype[code].push_back(t);
-  }
-  const at::ScalarType dtypes[3] = {at::kBFloat16, at::kHalf, at::kFloat};
-  for (int c = 0; c < 3; c++)
-    if (!gt.by_dtype[c].empty()) gt.handle[c] = tables.add({{&gt.by_dtype[c], dtypes[c]}});
-}
 
 void check_max_blocks(int64_t max_blocks) {
   TORCH_CHECK(max_blocks >= 1 && max_blocks <= (int64_t(1) << 16),
@@ -675,49 +678,58 @@ void run_sumsq(const std::vector<std::pair<int, tft::MultiTensorTable>>& tbs,
                                   stats.data_ptr<float>(), stream);
 }
 
-std::vector<std::pair<int, tft::MultiTensorTable>> grad_views(const TableSet& tables,
-                                                              const GradTables& gt) {
-  std::vector<std::pair<int, tft::MultiTensorTable>> out;
+// The sum of squares over every tensor, queued on `stream`: `stats`, a
+// 1-element fp32 device tensor, and the (dtype code, view) of every table it was
+// summed from. `tables` owns the device memory the views point into, so it
+// lives as long as a launch may still be queued on them.
+struct GradSumsq {
+  TableSet tables;
+  std::vector<std::pair<int, tft::MultiTensorTable>> views;
+  at::Tensor stats;
+};
+
+GradSumsq grad_sumsq_of(const TensorList& tensors, int64_t max_blocks, tft_stream stream) {
+  check_max_blocks(max_blocks);
+  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
+  GradSumsq s{TableSet(tensors[0], "grad norm"), {}, {}};
+  // one table per dtype present, all in the one TableSet
+  TensorList by_dtype[3];  // indexed by dtype_code
+  for (auto& t : tensors) {
+    const int code = dtype_code(t.scalar_type());
+    TORCH_CHECK(code >= 0, "unsupported dtype for grad norm: ", t.scalar_type());
+    by_dtype[code].push_back(t);
+  }
+  const at::ScalarType dtypes[3] = {at::kBFloat16, at::kHalf, at::kFloat};
+  int handle[3] = {-1, -1, -1};
   for (int c = 0; c < 3; c++)
-    if (gt.handle[c] >= 0) out.emplace_back(c, tables.table(gt.handle[c]));
-  return out;
+    if (!by_dtype[c].empty()) handle[c] = s.tables.add({{&by_dtype[c], dtypes[c]}});
+  s.tables.upload();
+  for (int c = 0; c < 3; c++)
+    if (handle[c] >= 0) s.views.emplace_back(c, s.tables.table(handle[c]));
+  s.stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
+  run_sumsq(s.views, max_blocks, s.stats, stream);
+  return s;
 }
 
 }  // namespace
 
 // Sum of squares over every tensor, as a 1-element fp32 device tensor.
 at::Tensor grad_sumsq(const std::vector<at::Tensor>& tensors, int64_t max_blocks) {
-  check_max_blocks(max_blocks);
-  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
-  TableSet tables(tensors[0], "grad norm");
-  GradTables gt;
-  add_grad_tables(tables, tensors, gt);
-  tables.upload();
-  auto stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
-  run_sumsq(grad_views(tables, gt), max_blocks, stats, current_stream());
-  return stats;
+  return grad_sumsq_of(tensors, max_blocks, current_stream()).stats;
 }
 
 // Norm + in-place scale sharing one table; norm_reduce (or None) sees the
 // 1-element sum of squares between the two. Returns the sum of squares.
 at::Tensor clip_grad_norm(const std::vector<at::Tensor>& tensors, double max_norm,
                           int64_t max_blocks, py::object norm_reduce) {
-  check_max_blocks(max_blocks);
   TORCH_CHECK(max_norm > 0.0, "max_norm must be > 0");
-  TORCH_CHECK(!tensors.empty(), "need at least one tensor");
-  TableSet tables(tensors[0], "grad norm");
-  GradTables gt;
-  add_grad_tables(tables, tensors, gt);
-  tables.upload();
-  auto stats = at::empty({1}, tensors[0].options().dtype(at::kFloat));
   auto stream = current_stream();
-  const auto views = grad_views(tables, gt);
-  run_sumsq(views, max_blocks, stats, stream);
-  if (!norm_reduce.is_none()) norm_reduce(stats);
-  for (auto& ct : views)
-    tft::launch_grad_scale(ct.first, ct.second, stats.data_ptr<float>(), (float)max_norm,
+  const GradSumsq s = grad_sumsq_of(tensors, max_blocks, stream);
+  if (!norm_reduce.is_none()) norm_reduce(s.stats);
+  for (auto& ct : s.views)
+    tft::launch_grad_scale(ct.first, ct.second, s.stats.data_ptr<float>(), (float)max_norm,
                            stream);
-  return stats;
+  return s.stats;
 }
 
 // FusedAdamW clip mode, one call per optimizer step. The tensor lists are flat
@@ -768,14 +780,11 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
   std::vector<int> h_update(ng);
   int64_t first = 0;
   for (int64_t g = 0; g < ng; g++) {
-    TORCH_CHECK(group_sizes[g] >= 0 && first + group_sizes[g] <= n);
-    std::vector<Column> cols = {{&params, at::kBFloat16},
-                                {&grads, at::kBFloat16},
-                                {&exp_avgs, at::kFloat},
-                                {&exp_avg_sqs, at::kFloat},
-                                {&steps, at::kInt, /*one_element=*/true}};
-    ra.add_column(cols);
-    h_update[g] = tables.add(cols, first, group_sizes[g]);
+    TORCH_CHECK(group_sizes[g] >= 0 && first + group_sizes[g] <= n,
+                "adamw_clip_step: group_sizes[", g, "] = ", group_sizes[g],
+                " does not fit the ", n, " tensors");
+    h_update[g] = tables.add(adamw_columns(params, grads, exp_avgs, exp_avg_sqs, &steps, ra),
+                             first, group_sizes[g]);
     first += group_sizes[g];
   }
   TORCH_CHECK(first == n, "group_sizes must cover every tensor");
@@ -786,18 +795,15 @@ void adamw_clip_step(const std::vector<at::Tensor>& params,
   run_sumsq({{tft::kBF16, tables.table(h_norm)}}, max_blocks, stats, stream);
   if (!norm_reduce.is_none()) norm_reduce(stats.narrow(0, 0, 1));
 
+  tft::AdamwLaunch a{};
+  a.rounding = ra.mode;
+  a.clip = true;
+  a.stats = stats.data_ptr<float>();
+  a.max_norm = (float)max_norm;
   for (int64_t g = 0; g < ng; g++) {
-    if (ra.mode == tft::kRoundNearest)
-      tft::launch_adamw_clip(tables.table(h_update[g]), (float)lrs[g], (float)beta1s[g],
-                             (float)beta2s[g], (float)epss[g], (float)weight_decays[g],
-                             stats.data_ptr<float>(), (float)max_norm, stream);
-    else
-      tft::launch_adamw_clip_rounded(ra.mode, tables.table(h_update[g]), (float)lrs[g],
-                                     (float)beta1s[g], (float)beta2s[g], (float)epss[g],
-                                     (float)weight_decays[g], stats.data_ptr<float>(),
-                                     (float)max_norm,
-                                     RoundingArgs::key(sr_seeds.empty() ? 0 : sr_seeds[g], 0),
-                                     stream);
+    a.tb = tables.table(h_update[g]);
+    a.key = RoundingArgs::key(sr_seeds.empty() ? 0 : sr_seeds[g], 0);
+    launch_adamw_update(a, lrs[g], beta1s[g], beta2s[g], epss[g], weight_decays[g], stream);
   }
   const auto st = tables.table(h_steps);
   tft::launch_adamw_bump_steps(st.col(0), st.n, stats.data_ptr<float>(),

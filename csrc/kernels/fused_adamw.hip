@@ -187,14 +187,25 @@ __global__ void adamw_kernel(MultiTensorTable tb, float lr, float beta1, float b
   }
 }
 
-void launch_adamw(MultiTensorTable tb, float lr, float beta1, float beta2,
-                  float eps, float weight_decay, float bias_correction1,
-                  float bias_correction2, hipStream_t stream) {
-  if (tb.total_blocks <= 0) return;
-  hipLaunchKernelGGL((adamw_kernel<false, kRoundNearest>), dim3((uint32_t)tb.total_blocks),
-                     dim3(kMtThreads), 0, stream, tb, lr, beta1, beta2, eps,
-                     weight_decay, bias_correction1, bias_correction2,
-                     (const float*)nullptr, 0.f);
+// adamw_kernel<kClip, kRound, Key...> with what the mode does not read
+// (kernels.h, AdamwLaunch) filled in: bias corrections of 1, no stats
+template <bool kClip, int kRound, typename... Key>
+static void launch_as(const AdamwLaunch& a, hipStream_t stream, Key... key) {
+  hipLaunchKernelGGL((adamw_kernel<kClip, kRound, Key...>), dim3((uint32_t)a.tb.total_blocks),
+                     dim3(kMtThreads), 0, stream, a.tb, a.lr, a.beta1, a.beta2, a.eps,
+                     a.weight_decay, kClip ? 1.f : a.bc1, kClip ? 1.f : a.bc2,
+                     kClip ? a.stats : (const float*)nullptr, kClip ? a.max_norm : 0.f, key...);
+}
+
+void launch_adamw(const AdamwLaunch& a, hipStream_t stream) {
+  if (a.tb.total_blocks <= 0) return;
+  if (a.rounding == kRoundStochastic)
+    a.clip ? launch_as<true, kRoundStochastic>(a, stream, a.key)
+           : launch_as<false, kRoundStochastic>(a, stream, a.key);
+  else if (a.rounding == kRoundMaster)
+    a.clip ? launch_as<true, kRoundMaster>(a, stream) : launch_as<false, kRoundMaster>(a, stream);
+  else
+    a.clip ? launch_as<true, kRoundNearest>(a, stream) : launch_as<false, kRoundNearest>(a, stream);
 }
 
 // One thread per participating tensor, after every group's update on the same
@@ -213,48 +224,6 @@ __global__ void adamw_bump_steps_kernel(const int64_t* __restrict__ step_ptrs,
   } else if (i == 0) {
     skipped[0] += 1;
   }
-}
-
-void launch_adamw_clip(MultiTensorTable tb, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, const float* stats,
-                       float max_norm, hipStream_t stream) {
-  if (tb.total_blocks <= 0) return;
-  hipLaunchKernelGGL((adamw_kernel<true, kRoundNearest>), dim3((uint32_t)tb.total_blocks),
-                     dim3(kMtThreads), 0, stream, tb, lr, beta1, beta2, eps,
-                     weight_decay, 1.f, 1.f, stats, max_norm);
-}
-
-// kClip with the two modes that are not kRoundNearest
-template <bool kClip>
-static void launch_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
-                           float beta2, float eps, float weight_decay, float bc1, float bc2,
-                           const float* stats, float max_norm, SrKey key,
-                           hipStream_t stream) {
-  if (tb.total_blocks <= 0) return;
-  const dim3 grid((uint32_t)tb.total_blocks), block(kMtThreads);
-  if (rounding == kRoundStochastic)
-    hipLaunchKernelGGL((adamw_kernel<kClip, kRoundStochastic, SrKey>), grid, block, 0, stream,
-                       tb, lr, beta1, beta2, eps, weight_decay, bc1, bc2, stats, max_norm,
-                       key);
-  else
-    hipLaunchKernelGGL((adamw_kernel<kClip, kRoundMaster>), grid, block, 0, stream, tb, lr,
-                       beta1, beta2, eps, weight_decay, bc1, bc2, stats, max_norm);
-}
-
-void launch_adamw_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
-                          float beta2, float eps, float weight_decay,
-                          float bias_correction1, float bias_correction2, SrKey key,
-                          hipStream_t stream) {
-  launch_rounded<false>(rounding, tb, lr, beta1, beta2, eps, weight_decay,
-                        bias_correction1, bias_correction2, nullptr, 0.f, key, stream);
-}
-
-void launch_adamw_clip_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
-                               float beta2, float eps, float weight_decay,
-                               const float* stats, float max_norm, SrKey key,
-                               hipStream_t stream) {
-  launch_rounded<true>(rounding, tb, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, stats,
-                       max_norm, key, stream);
 }
 
 void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,

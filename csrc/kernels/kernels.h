@@ -109,40 +109,34 @@ void launch_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, void* d
                          int Hq, int Hkv, int D, tft_stream stream);
 
 // fused_adamw.hip ----------------------------------------------------------
-// table: cols 0..3 = param, grad, exp_avg, exp_avg_sq (bf16, bf16, fp32, fp32)
-void launch_adamw(MultiTensorTable tb, float lr, float beta1, float beta2,
-                  float eps, float weight_decay, float bias_correction1,
-                  float bias_correction2, tft_stream stream);
-// clip mode: col 4 = the per-tensor device int32 step counts the bias
-// corrections come from; coefficient from stats[0] (global sum of squared
-// gradients); a non-finite norm stores nothing
-void launch_adamw_clip(MultiTensorTable tb, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, const float* stats,
-                       float max_norm, tft_stream stream);
-// finite norm: ++*step[t] for every tensor; else ++*skipped. norm_out[0] = norm
-void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,
-                             const float* stats, int32_t* skipped, float* norm_out,
-                             tft_stream stream);
-
-// How the step stores the parameter (docs/KERNELS.md, "Rounding modes"). The
-// launchers above are kRoundNearest; the two below take the other modes, each
-// with one more table column after the mode's last (4 plain, 5 clip):
-// kRoundStochastic the parameter's stream id (a number, not an address, below
-// 2^32), kRoundMaster its fp32 master copy. `key` is read by kRoundStochastic
-// alone; the clip mode takes the step word from the device step count + 1.
+// How the step stores the parameter (docs/KERNELS.md, "Rounding modes")
 enum AdamwRounding : int { kRoundNearest = 0, kRoundStochastic = 1, kRoundMaster = 2 };
 struct SrKey {
   uint32_t seed_lo, seed_hi;
   uint32_t step;  // the step count being taken, plain mode
 };
-void launch_adamw_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
-                          float beta2, float eps, float weight_decay,
-                          float bias_correction1, float bias_correction2, SrKey key,
-                          tft_stream stream);
-void launch_adamw_clip_rounded(int rounding, MultiTensorTable tb, float lr, float beta1,
-                               float beta2, float eps, float weight_decay,
-                               const float* stats, float max_norm, SrKey key,
-                               tft_stream stream);
+// One update launch. table: cols 0..3 = param, grad, exp_avg, exp_avg_sq (bf16,
+// bf16, fp32, fp32); with `clip`, col 4 = the per-tensor device int32 step
+// counts; then one more column for kRoundStochastic, the parameter's stream id
+// (a number, not an address, below 2^32), or for kRoundMaster, its fp32 master
+// copy. The fields up to `clip` are read by every mode, the rest by the mode
+// named; in clip mode a non-finite norm stores nothing and the bias corrections
+// and the stochastic step word come from the device step counts (+ 1).
+struct AdamwLaunch {
+  MultiTensorTable tb;
+  float lr, beta1, beta2, eps, weight_decay;
+  int rounding = kRoundNearest;
+  bool clip = false;
+  float bc1 = 1.f, bc2 = 1.f;    // plain: the host's bias corrections
+  const float* stats = nullptr;  // clip: stats[0] = global sum of squared gradients
+  float max_norm = 0.f;          // clip: the coefficient is min(1, max_norm / (norm + 1e-6))
+  SrKey key = {0, 0, 0};         // kRoundStochastic; clip reads the seed only
+};
+void launch_adamw(const AdamwLaunch& a, tft_stream stream);
+// finite norm: ++*step[t] for every tensor; else ++*skipped. norm_out[0] = norm
+void launch_adamw_bump_steps(const int64_t* step_ptrs, int n_tensors,
+                             const float* stats, int32_t* skipped, float* norm_out,
+                             tft_stream stream);
 
 // grad_norm.hip ------------------------------------------------------------
 // table: col 0 = the gradients. `grid` workgroups grid-stride over the

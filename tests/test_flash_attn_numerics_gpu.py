@@ -7,6 +7,7 @@ the two criteria used here refuse subtly wrong results. Also what the bindings
 do with empty inputs and with more batch * heads than a launch covers."""
 
 import functools
+import gc
 
 import pytest
 import torch
@@ -190,6 +191,10 @@ class TestBindingEdges:
         q, k = big(1, S, 128), big(1, S, 128)
         stat = big(1, S, dtype=torch.float32)
         ext = _ext()
+        # garbage of earlier tests (a pytest.raises traceback keeps its frame's
+        # tensors in a cycle) must go now: collected between the next two
+        # statements it would lower the peak below `before`
+        gc.collect()
         torch.cuda.synchronize()
         before = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
