@@ -1000,6 +1000,25 @@ struct FaArgs {
     doc_start = doc("doc_start", *ds);
     doc_end = doc("doc_end", *de);
   }
+  // acc / m / l of a carried softmax state and fa_bwd's dq_acc: private to
+  // the op, so held to exactly one form, dense fp32 [B,Hq,S] (+ [128] with
+  // head_dim) on q's device. `with` says what they came with ("state",
+  // "dq_acc"): neither goes with a document mask or with k longer than q.
+  void add_f32(const char* with, const char* name, const at::Tensor& t, bool head_dim) {
+    TORCH_CHECK(!doc_start.defined(), what, ": ", with,
+                " does not go with doc_start / doc_end");
+    TORCH_CHECK(ts[1].size(2) == q().size(2), what, ": ", with,
+                " needs k of q's sequence length, got ", ts[1].size(2), " against ",
+                q().size(2));
+    std::vector<int64_t> want = {q().size(0), q().size(1), q().size(2)};
+    if (head_dim) want.push_back(tft::kFaD);
+    TORCH_CHECK(t.scalar_type() == at::kFloat, what, ": ", name,
+                " must be an fp32 tensor, got ", t.scalar_type());
+    TORCH_CHECK(t.device() == q().device(), what, ": ", name, " must be on q's device");
+    TORCH_CHECK(t.sizes() == at::IntArrayRef(want) && t.is_contiguous(), what, ": ", name,
+                " must be a contiguous ", at::IntArrayRef(want), " tensor, got ", t.sizes(),
+                " with strides ", t.strides());
+  }
   // null without a mask
   const int* doc_start_ptr() const {
     return doc_start.defined() ? doc_start.data_ptr<int>() : nullptr;
@@ -1059,6 +1078,9 @@ struct FaArgs {
 
 }  // namespace
 
+// (acc, m, l): the softmax state a chain of fa_fwd calls carries (kernels.h)
+using FaState = std::tuple<at::Tensor, at::Tensor, at::Tensor>;
+
 at::Tensor fa_delta(at::Tensor dout, at::Tensor out) {
   FaArgs a("fa_delta", "dout", dout, /*seq_multiple=*/1);
   a.add("out", out);
@@ -1076,34 +1098,64 @@ at::Tensor fa_delta(at::Tensor dout, at::Tensor out) {
 std::vector<at::Tensor> fa_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                double scale, bool causal,
                                c10::optional<at::Tensor> doc_start,
-                               c10::optional<at::Tensor> doc_end) {
+                               c10::optional<at::Tensor> doc_end,
+                               c10::optional<FaState> state, bool last) {
   FaArgs a("fa_fwd", "q", q, /*seq_multiple=*/256);
   a.add_kv(k, v);
   a.add_doc(doc_start, doc_end, causal);
   a.check_grid();
-  auto out = a.out_like(0);
-  auto lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
-  if (a.empty()) return {out, lse};
-  auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
-  tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(),
-                     lse.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)k.size(1),
-                     (int)q.size(2), (int)k.size(2), (float)scale, causal, a.bshd,
-                     a.doc_start_ptr(), a.doc_end_ptr(), current_stream());
-  return {out, lse};
+  // the carried state (kernels.h): read when given, written unless last
+  const bool has_in = state.has_value();
+  at::Tensor acc, m, l;
+  if (has_in) {
+    std::tie(acc, m, l) = *state;
+    a.add_f32("state", "acc", acc, /*head_dim=*/true);
+    a.add_f32("state", "m", m, /*head_dim=*/false);
+    a.add_f32("state", "l", l, /*head_dim=*/false);
+  } else if (!last) {
+    const auto f32 = q.options().dtype(at::kFloat);
+    acc = at::empty({q.size(0), q.size(1), q.size(2), tft::kFaD}, f32);
+    m = at::empty({q.size(0), q.size(1), q.size(2)}, f32);
+    l = at::empty_like(m);
+    a.add_f32("last=False", "acc", acc, /*head_dim=*/true);
+  }
+  at::Tensor out, lse;
+  if (last) {
+    out = a.out_like(0);
+    lse = at::empty({q.size(0), q.size(1), q.size(2)}, q.options().dtype(at::kFloat));
+  }
+  if (!a.empty()) {
+    auto qc = a.in(0), kc = a.in(1), vc = a.in(2);
+    tft::launch_fa_fwd(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                       last ? out.data_ptr() : nullptr,
+                       last ? lse.data_ptr<float>() : nullptr, (int)q.size(0),
+                       (int)q.size(1), (int)k.size(1), (int)q.size(2), (int)k.size(2),
+                       (float)scale, causal, a.bshd, a.doc_start_ptr(), a.doc_end_ptr(),
+                       acc.defined() ? acc.data_ptr<float>() : nullptr,
+                       acc.defined() ? m.data_ptr<float>() : nullptr,
+                       acc.defined() ? l.data_ptr<float>() : nullptr, has_in, last,
+                       current_stream());
+  }
+  if (last) return {out, lse};
+  return {acc, m, l};
 }
 
 std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                at::Tensor dout, at::Tensor lse, at::Tensor delta,
                                double scale, bool causal,
                                c10::optional<at::Tensor> doc_start,
-                               c10::optional<at::Tensor> doc_end) {
+                               c10::optional<at::Tensor> doc_end,
+                               c10::optional<at::Tensor> dq_acc) {
   FaArgs a("fa_bwd", "q", q, /*seq_multiple=*/128);
   a.add_kv(k, v);
   a.add("dout", dout);
   a.add_doc(doc_start, doc_end, causal);
   a.check_grid();
+  if (dq_acc.has_value()) a.add_f32("dq_acc", "dq_acc", *dq_acc, /*head_dim=*/true);
   auto lsec = a.stat("lse", lse), deltac = a.stat("delta", delta);
-  auto dq = a.out_like(0), dk = a.out_like(1), dv = a.out_like(2);
+  // with dq_acc the kernel adds the unrounded dq to it and writes no bf16 dq
+  auto dq = dq_acc.has_value() ? *dq_acc : a.out_like(0);
+  auto dk = a.out_like(1), dv = a.out_like(2);
   // no query rows: keys that nothing attends to have zero gradients
   if (a.empty()) return {dq, dk.zero_(), dv.zero_()};
   auto qc = a.in(0), kc = a.in(1), vc = a.in(2), doc = a.in(3);
@@ -1111,7 +1163,8 @@ std::vector<at::Tensor> fa_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
                      lsec.data_ptr<float>(), deltac.data_ptr<float>(), dq.data_ptr(),
                      dk.data_ptr(), dv.data_ptr(), (int)q.size(0), (int)q.size(1),
                      (int)k.size(1), (int)q.size(2), (int)k.size(2), (float)scale, causal,
-                     a.bshd, a.doc_start_ptr(), a.doc_end_ptr(), current_stream());
+                     a.bshd, a.doc_start_ptr(), a.doc_end_ptr(),
+                     dq_acc.has_value() ? dq.data_ptr<float>() : nullptr, current_stream());
   return {dq, dk, dv};
 }
 
@@ -1210,13 +1263,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "diloco_outer_step with the pseudo-gradients decoded from a reduced fp8 pack");
   m.def("fa_fwd", &fa_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
         py::arg("causal"), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none(),
-        "flash-attention forward (bf16, D=128): returns (out, lse)");
+        py::arg("doc_end") = py::none(), py::arg("state") = py::none(),
+        py::arg("last") = true,
+        "flash-attention forward (bf16, D=128): returns (out, lse). state=(acc, m, l) "
+        "and last fold one key block of a longer stream: last=False returns the "
+        "state (updated in place when given) instead");
   m.def("fa_delta", &fa_delta);
   m.def("fa_bwd", &fa_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("dout"),
         py::arg("lse"), py::arg("delta"), py::arg("scale"), py::arg("causal"),
         py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none(),
-        "flash-attention backward (bf16, D=128): returns (dq, dk, dv)");
+        py::arg("dq_acc") = py::none(),
+        "flash-attention backward (bf16, D=128): returns (dq, dk, dv); with dq_acc "
+        "(fp32) the unrounded dq is added to it and it is the first tensor returned");
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd,
         "fused cross-entropy: returns row_loss, writes the gradient in place");
   m.def("mfma_probe", &mfma_probe, "mfma_f32_32x32x16_bf16 layout probe");

@@ -335,8 +335,19 @@ struct SmemDqDoc : SmemDq {
   alignas(16) int ds_row[kFaWaves][32];
 };
 
+// ACC (dq only): the accumulate variant. The pack holds dq_sum, a dense fp32
+// [B,Hq,S,D] whatever q's layout, and the epilogue adds to it the fp32 value
+// the plain kernel rounds to bf16; dq itself is not written. A row belongs to
+// one wave of one workgroup: a plain read-modify-write, no atomics, the same
+// bits every run. Ring attention sums a rank's dq over its key blocks this
+// way (docs/KERNELS.md, "Ring attention: carried state").
+template <class... R>
+__device__ inline float* dq_sum_of(float* p, R...) {
+  return p;
+}
+
 // ---- kernel 2: dQ ---------------------------------------------------------
-template <bool DOC, bool RECT, class... DocP>
+template <bool DOC, bool RECT, bool ACC, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
@@ -344,8 +355,9 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
     bf16* __restrict__ dq, int B, int Hq, int Hkv, int S, float scale,
     int causal, int bshd, DocP... docp) {
   static_assert(!(DOC && RECT), "no document mask with Sq != Sk");
-  static_assert(sizeof...(DocP) == (DOC || RECT ? 1 : 0),
-                "DOC takes doc_start, RECT the key length");
+  static_assert(!(ACC && (DOC || RECT)), "dq accumulates square and unmasked");
+  static_assert(sizeof...(DocP) == (DOC || RECT || ACC ? 1 : 0),
+                "DOC takes doc_start, RECT the key length, ACC dq_sum");
   __shared__ std::conditional_t<DOC, SmemDqDoc, SmemDq> sm;
   int Sk = S;
   if constexpr (RECT) Sk = rect_sk(docp...);
@@ -515,6 +527,20 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_bwd_dq_kernel(
   }
 
   if (!active) return;
+  if constexpr (ACC) {
+    // the lane owns element (row c_row(rg, half), column dt*32 + l31); a
+    // half's 32 lanes touch 128 contiguous bytes, as the bf16 store's 64
+    float* sum = dq_sum_of(docp...) +
+                 (((int64_t)b * Hq + hq) * S + ib * kFaBlk) * kFaD + l31;
+#pragma unroll
+    for (int dt = 0; dt < 4; dt++) {
+#pragma unroll
+      for (int rg = 0; rg < 16; rg++) {
+        sum[(int64_t)c_row(rg, half) * kFaD + dt * 32] += dq_acc[dt][rg];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int dt = 0; dt < 4; dt++) {
 #pragma unroll
@@ -575,7 +601,7 @@ void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout
                    const float* lse, const float* delta, void* dq, void* dk,
                    void* dv, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
-                   hipStream_t stream) {
+                   float* dq_sum, hipStream_t stream) {
   const int nblk = (S + kFaBlk * kFaWaves - 1) / (kFaBlk * kFaWaves);
   if (Sk != S) {  // dkdv's grid is over the key blocks, dq's over the query blocks
     hipLaunchKernelGGL((fa_bwd_dkdv_kernel<false, true, int>),
@@ -583,7 +609,7 @@ void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout
                        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout,
                        lse, delta, (bf16*)dk, (bf16*)dv, B, Hq, Hkv, S, scale,
                        causal ? 1 : 0, bshd ? 1 : 0, Sk);
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, true, int>), dim3(nblk, B * Hq),
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, true, false, int>), dim3(nblk, B * Hq),
                        dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq,
                        Hkv, S, scale, causal ? 1 : 0, bshd ? 1 : 0, Sk);
@@ -595,7 +621,7 @@ void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout
                        (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta,
                        (bf16*)dk, (bf16*)dv, B, Hq, Hkv, S, scale, 1, bshd ? 1 : 0,
                        doc_start, doc_end);
-    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, false, const int*>), dim3(nblk, B * Hq),
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<true, false, false, const int*>), dim3(nblk, B * Hq),
                        dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq,
                        Hkv, S, scale, 1, bshd ? 1 : 0, doc_start);
@@ -605,7 +631,14 @@ void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout
                      dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, B, Hq,
                      Hkv, S, scale, causal ? 1 : 0, bshd ? 1 : 0);
-  hipLaunchKernelGGL((fa_bwd_dq_kernel<false, false>), dim3(nblk, B * Hq),
+  if (dq_sum != nullptr) {  // square, no mask (bindings); dq is not written
+    hipLaunchKernelGGL((fa_bwd_dq_kernel<false, false, true, float*>), dim3(nblk, B * Hq),
+                       dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq, Hkv,
+                       S, scale, causal ? 1 : 0, bshd ? 1 : 0, dq_sum);
+    return;
+  }
+  hipLaunchKernelGGL((fa_bwd_dq_kernel<false, false, false>), dim3(nblk, B * Hq),
                      dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (const bf16*)dout, lse, delta, (bf16*)dq, B, Hq, Hkv, S,
                      scale, causal ? 1 : 0, bshd ? 1 : 0);

@@ -39,6 +39,14 @@
 //   positions the causal tests see are shifted down by Sk - Sq, a multiple of
 //   256: wave-uniform, so the diagonal tiles run the square kernel's code.
 //
+//   Carried state (CARRY variant): one launch folds ONE key block of a longer
+//   key stream into the online-softmax state and hands that state on raw:
+//   o_acc (unnormalised), m_run (log2 domain) and l_run go out to three dense
+//   fp32 tensors and come back in at the next launch, so a chain of launches
+//   over key blocks does the arithmetic of one launch over their
+//   concatenation, in the same order (ring attention: docs/KERNELS.md, "Ring
+//   attention: carried state"). The tile loop is untouched.
+//
 // MFMA lane mappings (mfma_probe.hip):
 //   A: row=lane&31, k=(lane>>5)*8+m   B: k=(lane>>5)*8+m, col=lane&31
 //   C/D: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
@@ -107,15 +115,29 @@ __device__ inline float half_combine_sum(float v) {
 // the plain instantiation keeps its parameter list and its code.
 // RECT: the rectangular variant (docs/KERNELS.md, "Rectangular attention").
 // S is then the query length and the pack holds the key length.
-template <bool DOC, bool RECT, class... DocP>
+// CARRY: the carried-state variant; the pack holds one FaCarry.
+struct FaCarry {
+  float* acc;  // [B,Hq,S,D] unnormalised o_acc, dense whatever q's layout
+  float* m;    // [B,Hq,S]   m_run, log2 domain
+  float* l;    // [B,Hq,S]   l_run
+  int has_in;  // the state of earlier key blocks comes in
+  int last;    // this is the stream's last block: out / lse, no state out
+};
+template <class... R>
+__device__ inline const FaCarry& carry_of(const FaCarry& c, R...) {
+  return c;
+}
+
+template <bool DOC, bool RECT, bool CARRY, class... DocP>
 __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, bf16* __restrict__ out,
     float* __restrict__ lse, int B, int Hq, int Hkv, int S, float scale,
     int causal, int bshd, DocP... docp) {
   static_assert(!(DOC && RECT), "no document mask with Sq != Sk");
-  static_assert(sizeof...(DocP) == (DOC || RECT ? 1 : 0),
-                "DOC takes doc_start, RECT the key length");
+  static_assert(!(CARRY && (DOC || RECT)), "the carried state is square and unmasked");
+  static_assert(sizeof...(DocP) == (DOC || RECT || CARRY ? 1 : 0),
+                "DOC takes doc_start, RECT the key length, CARRY a FaCarry");
   __shared__ SmemFwd sm;
   // keys: Sk of them, and key j sits at j - off on the causal diagonal of the
   // query rows
@@ -194,6 +216,25 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
       DOC ? load_tiles<64>(k_base + (int64_t)j0 * kFwdKvBlk * kv_ld,
                            v_base + (int64_t)j0 * kFwdKvBlk * kv_ld, kv_ld)
           : load_tiles<64>(k_base, v_base, kv_ld);
+  // CARRY: the state of the key blocks before this one. Issued behind tile 0's
+  // loads, so it retires under their HBM latency. m / l sit at the lane's own
+  // row (both halves read the same value); o_acc[dt][r] is row c_row(r, half),
+  // column dt*32 + l31: a half's 32 lanes read 128 contiguous bytes.
+  if constexpr (CARRY) {
+    const FaCarry& cy = carry_of(docp...);
+    if (cy.has_in && active) {
+      m_run = cy.m[lse_head + q_glob];
+      l_run = cy.l[lse_head + q_glob];
+      const float* acc_in = cy.acc + (lse_head + my_q0) * kFaD + l31;
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          o_acc[dt][r] = acc_in[(int64_t)c_row(r, half) * kFaD + dt * 32];
+        }
+      }
+    }
+  }
   for (int j = DOC ? j0 : 0; j < nT; j++) {
     const int cur = j & 1;
     write_tiles(&sm.k_img[cur], &sm.v_img[cur], staged);
@@ -345,6 +386,27 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
 
   if (!active) return;
 
+  // CARRY, more key blocks to come: the state goes out as it is, no division
+  // and no log. In place is safe: a wave wrote only the rows it read.
+  if constexpr (CARRY) {
+    const FaCarry& cy = carry_of(docp...);
+    if (!cy.last) {
+      float* acc_out = cy.acc + (lse_head + my_q0) * kFaD + l31;
+#pragma unroll
+      for (int dt = 0; dt < 4; dt++) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          acc_out[(int64_t)c_row(r, half) * kFaD + dt * 32] = o_acc[dt][r];
+        }
+      }
+      if (half == 0) {
+        cy.m[lse_head + q_glob] = m_run;
+        cy.l[lse_head + q_glob] = l_run;
+      }
+      return;
+    }
+  }
+
   // epilogue: O /= l (l lives at lane q=l31; O rows are c_row) and store.
   // bc is wave-private and the write/read are same-wave DS ops, ordered by
   // the LDS pipeline — no barrier (and a workgroup barrier would deadlock:
@@ -370,25 +432,34 @@ __global__ __launch_bounds__(kFaThreads, 1) void fa_fwd_kernel(
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
                    float* lse, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
+                   float* st_acc, float* st_m, float* st_l, bool has_in, bool last,
                    hipStream_t stream) {
   const int rows_per_wg = kFaWaves * kFaBlk;
   const int nblk = (S + rows_per_wg - 1) / rows_per_wg;
   (void)doc_end;  // the forward is query-centric: doc_start says it all
+  if (st_acc != nullptr) {  // a state goes in or out: square, no mask (bindings)
+    const FaCarry cy{st_acc, st_m, st_l, has_in ? 1 : 0, last ? 1 : 0};
+    hipLaunchKernelGGL((fa_fwd_kernel<false, false, true, FaCarry>), dim3(nblk, B * Hq),
+                       dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
+                       (const bf16*)v, (bf16*)out, lse, B, Hq, Hkv, S, scale,
+                       causal ? 1 : 0, bshd ? 1 : 0, cy);
+    return;
+  }
   if (doc_start != nullptr) {
-    hipLaunchKernelGGL((fa_fwd_kernel<true, false, const int*>), dim3(nblk, B * Hq),
+    hipLaunchKernelGGL((fa_fwd_kernel<true, false, false, const int*>), dim3(nblk, B * Hq),
                        dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, lse, B, Hq, Hkv, S, scale, 1,
                        bshd ? 1 : 0, doc_start);
     return;
   }
   if (Sk != S) {  // the grid is over the query blocks
-    hipLaunchKernelGGL((fa_fwd_kernel<false, true, int>), dim3(nblk, B * Hq),
+    hipLaunchKernelGGL((fa_fwd_kernel<false, true, false, int>), dim3(nblk, B * Hq),
                        dim3(kFaThreads), 0, stream, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (bf16*)out, lse, B, Hq, Hkv, S, scale,
                        causal ? 1 : 0, bshd ? 1 : 0, Sk);
     return;
   }
-  hipLaunchKernelGGL((fa_fwd_kernel<false, false>), dim3(nblk, B * Hq), dim3(kFaThreads),
+  hipLaunchKernelGGL((fa_fwd_kernel<false, false, false>), dim3(nblk, B * Hq), dim3(kFaThreads),
                      0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v,
                      (bf16*)out, lse, B, Hq, Hkv, S, scale, causal ? 1 : 0,
                      bshd ? 1 : 0);

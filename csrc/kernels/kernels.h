@@ -185,22 +185,30 @@ void launch_outer_sgd_fp8(int dtype_code, bool has_momentum, MultiTensorTable tb
 // kernel. Sk > S is the rectangular one (fa_layout.h): both multiples of 256,
 // the causal diagonal aligned bottom-right, no document mask; q / out / lse
 // keep the query length S.
+// st_acc / st_m / st_l: the carried softmax state, dense fp32 [B,Hq,S,128] /
+// [B,Hq,S] / [B,Hq,S], all null for a whole forward. With them the launch
+// folds ONE key block (Sk == S, no mask) of a longer key stream: has_in reads
+// the state of the blocks before it, and it ends in out / lse when last, in
+// the updated state (in place) when not.
 void launch_fa_fwd(const void* q, const void* k, const void* v, void* out,
                    float* lse, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
+                   float* st_acc, float* st_m, float* st_l, bool has_in, bool last,
                    tft_stream stream);
 
 // flash_attn_bwd.hip --------------------------------------------------------
 // tensors and layouts as in the forward; delta: dense fp32 [B,Hq,S], the row
 // sums of dout * o. launch_fa_bwd needs S % 128 == 0; with Sk > S, as in the
-// forward, dq has q's shape and dk / dv have k's.
+// forward, dq has q's shape and dk / dv have k's. dq_sum: null, or a dense fp32
+// [B,Hq,S,128] that the unrounded dq is added to (Sk == S, no mask); dq is not
+// written then.
 void launch_fa_delta(const void* dout, const void* o, float* delta,
                      int64_t rows, int Hq, int S, bool bshd, tft_stream stream);
 void launch_fa_bwd(const void* q, const void* k, const void* v, const void* dout,
                    const float* lse, const float* delta, void* dq, void* dk,
                    void* dv, int B, int Hq, int Hkv, int S, int Sk, float scale,
                    bool causal, bool bshd, const int* doc_start, const int* doc_end,
-                   tft_stream stream);
+                   float* dq_sum, tft_stream stream);
 
 // fused_cross_entropy.hip ---------------------------------------------------
 // logits: bf16 [rows, V] contiguous, overwritten with the gradient when

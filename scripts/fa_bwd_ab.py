@@ -34,8 +34,11 @@ import torch
 from torchft_amd.ops import hip_ext
 
 # launch_fa_bwd as it is now (the key length after S, given as S here; two
-# document-mask arrays before the stream, passed as null), as it was before
-# the rectangular kernels and as it was before the document mask
+# document-mask arrays and the fp32 dq sum before the stream, passed as null),
+# as it was before the accumulating dq, before the rectangular kernels and
+# before the document mask
+_SYM_DQ_SUM = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
+               "iiiiifbbPKiS6_PfP12ihipStream_t")
 _SYM = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
         "iiiiifbbPKiS6_P12ihipStream_t")
 _SYM_NO_SK = ("_ZN11torchft_amd13launch_fa_bwdEPKvS1_S1_S1_PKfS3_PvS4_S4_"
@@ -49,14 +52,15 @@ class Build:
     def __init__(self, spec):
         self.name, path = spec.split("=", 1)
         lib = ctypes.CDLL(os.path.abspath(path))
-        self.sk_arg = hasattr(lib, _SYM)
+        self.dq_sum_arg = hasattr(lib, _SYM_DQ_SUM)
+        self.sk_arg = self.dq_sum_arg or hasattr(lib, _SYM)
         self.doc_args = self.sk_arg or hasattr(lib, _SYM_NO_SK)
-        self.fn = getattr(lib, _SYM if self.sk_arg else
+        self.fn = getattr(lib, _SYM_DQ_SUM if self.dq_sum_arg else _SYM if self.sk_arg else
                           _SYM_NO_SK if self.doc_args else _SYM_NO_DOC)
         self.fn.restype = None
         self.fn.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * (5 if self.sk_arg else 4) + [
             ctypes.c_float, ctypes.c_bool, ctypes.c_bool] + [
-            ctypes.c_void_p] * (3 if self.doc_args else 1)
+            ctypes.c_void_p] * (self.dq_sum_arg + (3 if self.doc_args else 1))
 
     def __call__(self, p, out):
         B, Hq, S = p["q"].shape[0], p["q"].shape[1], p["q"].shape[2]
@@ -65,7 +69,7 @@ class Build:
                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
                 B, Hq, p["k"].shape[1], S, *((S,) if self.sk_arg else ()),
                 D ** -0.5, p["causal"], p["bshd"],
-                *((None, None) if self.doc_args else ()),
+                *((None, None) if self.doc_args else ()), *((None,) if self.dq_sum_arg else ()),
                 torch.cuda.current_stream().cuda_stream)
 
 

@@ -306,5 +306,6 @@ from torchft_amd.ops.diloco import (  # noqa: E402,F401
 from torchft_amd.ops.flash_attention import (  # noqa: E402,F401
     DocMask,
     flash_attention,
+    flash_attention_fold,
     flash_attention_rect,
 )

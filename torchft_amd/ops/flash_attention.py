@@ -27,6 +27,11 @@ key j iff j <= i + Sk - Sq), which is what a context-parallel rank computes.
 Both lengths are multiples of 256 on the kernel path, and the hand-written
 forward always runs there: the backward needs its logsumexp under exactly this
 mask. docs/KERNELS.md, "Rectangular attention".
+
+Carried state: ``flash_attention_fold(q, k, v, state)`` folds one key block
+into the running online-softmax state of q's rows, forward only: a chain of
+folds is attention over the concatenated blocks, which is what a ring-attention
+rank computes hop by hop. docs/KERNELS.md, "Ring attention: carried state".
 """
 
 from __future__ import annotations
@@ -237,6 +242,80 @@ def flash_attention(
     return F.scaled_dot_product_attention(
         q, k, v, is_causal=causal, scale=scale, enable_gqa=q.shape[1] != k.shape[1]
     )
+
+
+def _fold_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """``_supported`` plus the forward kernel's S % 256 == 0."""
+    return _supported(q, k) and q.shape[2] % 256 == 0
+
+
+def flash_attention_fold(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    state=None,
+    *,
+    causal: bool = False,
+    last: bool = False,
+    scale: Optional[float] = None,
+):
+    """Fold one key block ([B, Hkv, S, D], as long as q) into the running
+    online-softmax state of q's rows ([B, Hq, S, D]): a chain of folds over
+    key blocks is attention over their concatenation, without a per-block
+    ``out`` / ``lse`` and their merge. What a ring-attention rank does per hop.
+
+    ``state`` is what the previous fold returned, ``None`` for the first
+    block. ``causal`` masks this block as the diagonal one (key j visible to
+    row i iff j <= i). Returns the new state, or ``(out, lse)`` with
+    ``last=True``: ``out`` in q's dtype, ``lse`` fp32 ``[B, Hq, S]``.
+
+    The state is opaque: an unnormalised accumulator, a running maximum and a
+    running denominator, whose conventions belong to the path that made it. It
+    must go back into the same path, and a state that is passed in may be
+    updated in place. Forward only: nothing here is recorded by autograd
+    (``parallel.cp.ring_rank_attention`` supplies the backward).
+
+    Where the kernels apply (a HIP device, bf16, D = 128, S % 256 == 0, heads
+    dividing, TORCHFT_AMD_CUSTOM_FA not 0, the extension built) each fold is
+    one launch of the forward kernel's carried-state variant, which reads and
+    writes its registers' state raw: the chain does the arithmetic of a single
+    launch over all the keys, in the same order (docs/KERNELS.md, "Ring
+    attention: carried state"). Everywhere else it is the same recurrence in
+    fp32 torch."""
+    if k.shape[2] != q.shape[2]:
+        raise ValueError(f"a key block has q's length {q.shape[2]}, got {k.shape[2]}")
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    with torch.no_grad():
+        if _fold_supported(q, k):
+            return tuple(hip_ext().fa_fwd(q, k, v, scale, causal, state=state, last=last))
+        return _fold_torch(q, k, v, state, causal, last, scale)
+
+
+def _fold_torch(q, k, v, state, causal, last, scale):
+    """The online-softmax recurrence in fp32, natural-log ``m``."""
+    B, Hq, S, _ = q.shape
+    rep = Hq // k.shape[1]
+    kf = k.float().repeat_interleave(rep, dim=1)
+    vf = v.float().repeat_interleave(rep, dim=1)
+    s = torch.matmul(q.float(), kf.transpose(-2, -1)) * scale
+    if causal:
+        s = s.masked_fill(~torch.ones(S, S, dtype=torch.bool, device=q.device).tril_(),
+                          float("-inf"))
+    if state is None:
+        acc = torch.zeros(B, Hq, S, v.shape[-1], dtype=torch.float32, device=q.device)
+        m = torch.full((B, Hq, S), -1e30, dtype=torch.float32, device=q.device)
+        l = torch.zeros_like(m)
+    else:
+        acc, m, l = state
+    m_new = torch.maximum(m, s.amax(-1))
+    alpha = torch.exp(m - m_new)
+    p = torch.exp(s - m_new.unsqueeze(-1))
+    acc = acc * alpha.unsqueeze(-1) + torch.matmul(p, vf)
+    l = l * alpha + p.sum(-1)
+    if last:
+        return (acc / l.unsqueeze(-1)).to(q.dtype), m_new + torch.log(l)
+    return acc, m_new, l
 
 
 def _rect_supported(q: torch.Tensor, k: torch.Tensor) -> bool:

@@ -15,7 +15,9 @@ HBM3E, and the gather is a large contiguous allgather that RCCL drives over
 all 7 xGMI links. This is the scheme Llama-3's own long-context training
 used; a ring-attention (block-rotating) variant saves the KV residency at
 the cost of 2(W-1) p2p hops per layer and is the planned upgrade for
->512k contexts.
+>512k contexts (``ring_attention`` below; with ``TORCHFT_AMD_RING_FA=1`` its
+compute runs on the hand-written kernels, the softmax state carried from hop
+to hop: docs/KERNELS.md, "Ring attention: carried state").
 
 Backward: dK/dV are computed for the full context on every rank and
 reduce-scattered (sum) back to the owning shard.
@@ -36,15 +38,27 @@ import torch
 import torch.nn.functional as F
 from torch.distributed.distributed_c10d import AllgatherOptions, AllreduceOptions, ReduceOp
 
-from torchft_amd.ops.flash_attention import _rect_supported, flash_attention_rect
+from torchft_amd.ops import hip_ext
+from torchft_amd.ops.flash_attention import (
+    _fold_supported,
+    _rect_supported,
+    flash_attention_fold,
+    flash_attention_rect,
+)
 from torchft_amd.process_group import ProcessGroup
 
 _ENV_RECT = "TORCHFT_AMD_CP_RECT"
+_ENV_RING_FA = "TORCHFT_AMD_RING_FA"
 
 
 def cp_rect_enabled() -> bool:
     """The rectangular attention kernels under CP (opt-in)."""
     return os.environ.get(_ENV_RECT, "0") in ("1", "true", "True")
+
+
+def ring_fa_enabled() -> bool:
+    """The hand-written kernels under ring attention (opt-in)."""
+    return os.environ.get(_ENV_RING_FA, "0") in ("1", "true", "True")
 
 
 def shard_sequence(t: torch.Tensor, rank: int, world: int, dim: int = 1) -> torch.Tensor:
@@ -377,6 +391,124 @@ def _merge_block(out_acc, lse_acc, out_b, lse_b):
     return out_acc, new_lse
 
 
+def _ring_fused(fused: Optional[bool], q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Whether a ring's blocks run on the hand-written kernels: asked for
+    (``fused``; None reads TORCHFT_AMD_RING_FA) and the kernels apply."""
+    want = ring_fa_enabled() if fused is None else fused
+    return bool(want) and _fold_supported(q, k)
+
+
+def _ring_rep(fused: bool, q: torch.Tensor, k: torch.Tensor) -> int:
+    """How often aten's flash needs a KV block repeated along the heads. The
+    hand-written kernels are GQA-native: never."""
+    rep = q.shape[1] // k.shape[1]
+    if fused or (rep > 1 and _native_gqa_ok(q.device.type, q.dtype)):
+        rep = 1
+    return rep
+
+
+def _ring_fold(fused, q, k_b, v_b, state, blk_causal, last, rep):
+    """Fold one KV block into a rank's running state; returns (state, aux).
+
+    Fused: ``flash_attention_fold``, the kernel's own state handed on raw, and
+    ``(out, lse)`` comes back from the fold that is told it is the ``last``.
+    Otherwise aten's flash forward on the block and ``_merge_block`` into
+    ``(out_acc fp32, lse_acc)``; ``aux`` is what its backward wants back."""
+    if fused:
+        return flash_attention_fold(q, k_b, v_b, state, causal=blk_causal, last=last), None
+    if state is None:
+        B, Hq, s, D = q.shape
+        state = (torch.zeros(B, Hq, s, D, dtype=torch.float32, device=q.device),
+                 torch.full((B, Hq, s), float("-inf"), dtype=torch.float32, device=q.device))
+    o_b, l_b, aux = _flash_fwd_raw(q, _expand_kv(k_b, rep), _expand_kv(v_b, rep),
+                                   causal=blk_causal)
+    return _merge_block(*state, o_b, l_b), aux
+
+
+def _ring_bwd_prepare(fused, dout, out):
+    """Once per backward, before the blocks: the fused path's delta."""
+    return hip_ext().fa_delta(dout, out) if fused else None
+
+
+def _ring_block_bwd(fused, dout, q, k_b, v_b, out, lse, delta, blk_causal, aux, rep, dq):
+    """One block's backward with the MERGED out / lse (the identity
+    ``_MergedFlashAttn`` states). Adds the block's dq into ``dq`` (fp32) and
+    returns its (dk, dv) per KV head.
+
+    Fused: dkdv + the accumulating dq kernel, which adds its unrounded fp32
+    dq into ``dq`` itself: no per-block dq, no fp32 copy, no head expansion.
+    Otherwise aten's flash backward and the sum over the repeated heads."""
+    if fused:
+        _, dk_b, dv_b = hip_ext().fa_bwd(q, k_b, v_b, dout, lse, delta,
+                                         q.shape[-1] ** -0.5, blk_causal, dq_acc=dq)
+        return dk_b, dv_b
+    dq_b, dk_b, dv_b = _flash_bwd_raw(dout, q, _expand_kv(k_b, rep), _expand_kv(v_b, rep),
+                                      out, lse, blk_causal, aux)
+    dq += dq_b.float()
+    if rep == 1:
+        return dk_b.float(), dv_b.float()
+    B, Hkv, s, D = k_b.shape
+    return (dk_b.view(B, Hkv, rep, s, D).float().sum(2),
+            dv_b.view(B, Hkv, rep, s, D).float().sum(2))
+
+
+class _RingRank(torch.autograd.Function):
+    """``ring_rank_attention``: q [B,Hq,s,D] against n KV blocks in hop order."""
+
+    @staticmethod
+    def forward(ctx, q, causal_block, fused, n, *kv):
+        q = q.contiguous()
+        ks, vs = [t.contiguous() for t in kv[:n]], [t.contiguous() for t in kv[n:]]
+        fused = _ring_fused(fused, q, ks[0])
+        rep = _ring_rep(fused, q, ks[0])
+        state, auxs = None, []
+        for i in range(n):
+            state, aux = _ring_fold(fused, q, ks[i], vs[i], state, i == causal_block,
+                                    i == n - 1, rep)
+            auxs.append(aux)
+        out, lse = state
+        out = out.to(q.dtype)
+        ctx.save_for_backward(q, out, lse, *ks, *vs)
+        ctx.causal_block, ctx.fused, ctx.rep, ctx.n, ctx.auxs = causal_block, fused, rep, n, auxs
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, out, lse, *kv = ctx.saved_tensors
+        n, fused = ctx.n, ctx.fused
+        dout = dout.contiguous()
+        delta = _ring_bwd_prepare(fused, dout, out)
+        dq = torch.zeros_like(q, dtype=torch.float32)
+        dks, dvs = [], []
+        for i in range(n):
+            dk_b, dv_b = _ring_block_bwd(fused, dout, q, kv[i], kv[n + i], out, lse, delta,
+                                         i == ctx.causal_block, ctx.auxs[i], ctx.rep, dq)
+            dks.append(dk_b.to(q.dtype))
+            dvs.append(dv_b.to(q.dtype))
+        return (dq.to(q.dtype), None, None, None, *dks, *dvs)
+
+
+def ring_rank_attention(q, k_blocks, v_blocks, causal_block: Optional[int],
+                        fused: Optional[bool] = None) -> torch.Tensor:
+    """What one ring-attention rank computes from the KV blocks it meets, in
+    hop order, without the ring: the counterpart of :func:`cp_rank_attention`.
+
+    q [B, Hq, s, D]; k_blocks / v_blocks: lists of [B, Hkv, s, D], every one
+    visible to the rank. ``causal_block`` is the index of the one block that is
+    causal (the rank's own, index 0 in ring order), None for none. Returns
+    ``out`` [B, Hq, s, D]; autograd gives q's gradient and every block's.
+
+    ``fused`` (None: TORCHFT_AMD_RING_FA, default off): where the kernels
+    apply (a HIP device, bf16, D = 128, s % 256 == 0, heads dividing,
+    TORCHFT_AMD_CUSTOM_FA not 0, the extension built) every block is one
+    ``flash_attention_fold`` launch with the softmax state carried raw, and
+    the backward is ``fa_delta`` once, then dkdv + accumulating dq per block.
+    Otherwise aten's flash per block with the LSE merge."""
+    n = len(k_blocks)
+    assert n > 0 and n == len(v_blocks), "one v block per k block, at least one"
+    return _RingRank.apply(q, causal_block, fused, n, *k_blocks, *v_blocks)
+
+
 class _RingAttention(torch.autograd.Function):
     """Causal CP attention with ring-rotated KV blocks.
 
@@ -394,21 +526,20 @@ class _RingAttention(torch.autograd.Function):
     owning shards. Peak memory in backward matches the all-gather-KV
     scheme; the ring saves the FORWARD residency, which is what persists
     across the whole layer stack of a training step.
+
+    The compute of both is ``_ring_fold`` / ``_ring_block_bwd``; ``fused``
+    puts them on the hand-written kernels (``ring_rank_attention``).
     """
 
     @staticmethod
-    def forward(ctx, q, k_shard, v_shard, pg, rank, world, causal):
+    def forward(ctx, q, k_shard, v_shard, pg, rank, world, causal, fused=None):
         # layouts: q [B,Hq,s,D]; k_shard/v_shard [B,Hkv,s,D]
-        B, Hq, s, D = q.shape
         q = q.contiguous()
-        out_acc = torch.zeros(B, Hq, s, D, dtype=torch.float32, device=q.device)
-        lse_acc = torch.full((B, Hq, s), float("-inf"), dtype=torch.float32,
-                             device=q.device)
-
-        Hkv = k_shard.shape[1]
-        rep = Hq // Hkv
-        if rep > 1 and _native_gqa_ok(q.device.type, q.dtype):
-            rep = 1
+        fused = _ring_fused(fused, q, k_shard)
+        rep = _ring_rep(fused, q, k_shard)
+        # the last hop whose block this rank sees
+        last_hop = rank if causal else world - 1
+        state = None
 
         cur_k, cur_v = k_shard.contiguous(), v_shard.contiguous()
         nxt = (rank + 1) % world
@@ -431,20 +562,18 @@ class _RingAttention(torch.autograd.Function):
                 ws.wait()
                 wr.wait()
             if not causal or owner <= rank:
-                kb = _expand_kv(cur_k, rep)
-                vb = _expand_kv(cur_v, rep)
                 blk_causal = causal and owner == rank
-                o_b, l_b, aux = _flash_fwd_raw(q, kb, vb, causal=blk_causal)
-                aux_by_owner[owner] = aux
-                out_acc, lse_acc = _merge_block(out_acc, lse_acc, o_b, l_b)
+                state, aux_by_owner[owner] = _ring_fold(
+                    fused, q, cur_k, cur_v, state, blk_causal, hop == last_hop, rep)
             if hop < world - 1:
                 cur_k = recv_buf[0].view_as(cur_k).contiguous()
                 cur_v = recv_buf[1].view_as(cur_v).contiguous()
 
+        out_acc, lse_acc = state
         out = out_acc.to(q.dtype)
         ctx.save_for_backward(q, k_shard, v_shard, out, lse_acc)
         ctx.pg, ctx.rank, ctx.world, ctx.causal = pg, rank, world, causal
-        ctx.rep = rep
+        ctx.rep, ctx.fused = rep, fused
         ctx.aux_by_owner = aux_by_owner  # dropout-0 flash bwd side args
         return out
 
@@ -452,7 +581,7 @@ class _RingAttention(torch.autograd.Function):
     def backward(ctx, dout):
         q, k_shard, v_shard, out, lse = ctx.saved_tensors
         pg, rank, world, causal = ctx.pg, ctx.rank, ctx.world, ctx.causal
-        rep = ctx.rep
+        rep, fused = ctx.rep, ctx.fused
         B, Hkv, s, D = k_shard.shape
         dout = dout.contiguous()
 
@@ -468,26 +597,18 @@ class _RingAttention(torch.autograd.Function):
         dk_full = torch.zeros(world, B, Hkv, s, D, dtype=torch.float32,
                               device=q.device)
         dv_full = torch.zeros_like(dk_full)
+        delta = _ring_bwd_prepare(fused, dout, out)
         for o in range(world):
             if causal and o > rank:
                 continue
-            kb = _expand_kv(gath[o, 0].to(q.dtype).contiguous(), rep)
-            vb = _expand_kv(gath[o, 1].to(q.dtype).contiguous(), rep)
+            kb = gath[o, 0].to(q.dtype).contiguous()
+            vb = gath[o, 1].to(q.dtype).contiguous()
             blk_causal = causal and o == rank
             # flash bwd consumes the MERGED out/lse: exp(S_b - lse) is the
             # global softmax restricted to block b's columns
-            dq_b, dk_b, dv_b = _flash_bwd_raw(
-                dout, q, kb, vb, out, lse, blk_causal, ctx.aux_by_owner[o]
-            )
-            dq += dq_b.float()
-
-            def fold(d):
-                if rep == 1:
-                    return d.float()
-                return d.view(B, Hkv, rep, s, D).float().sum(2)
-
-            dk_full[o] = fold(dk_b)
-            dv_full[o] = fold(dv_b)
+            dk_full[o], dv_full[o] = _ring_block_bwd(
+                fused, dout, q, kb, vb, out, lse, delta, blk_causal,
+                ctx.aux_by_owner[o], rep, dq)
 
         # sum contributions from every rank, keep own shard
         opts = AllreduceOptions()
@@ -496,7 +617,7 @@ class _RingAttention(torch.autograd.Function):
         pg.allreduce([grads], opts).wait()
         dk = grads[0].view(world, B, Hkv, s, D)[rank].to(k_shard.dtype)
         dv = grads[1].view(world, B, Hkv, s, D)[rank].to(v_shard.dtype)
-        return dq.to(q.dtype), dk, dv, None, None, None, None
+        return dq.to(q.dtype), dk, dv, None, None, None, None, None
 
 
 def ring_attention(
@@ -507,17 +628,21 @@ def ring_attention(
     rank: int,
     world: int,
     causal: bool = True,
+    fused: Optional[bool] = None,
 ) -> torch.Tensor:
     """Ring-attention CP: same contract as :func:`cp_attention` ([B, s, H, D]
     shards in/out) but with ring-rotated KV — forward KV residency is two
-    shards instead of the full context."""
+    shards instead of the full context. ``fused`` (None: TORCHFT_AMD_RING_FA):
+    the hand-written kernels with the softmax state carried between hops,
+    where they apply (:func:`ring_rank_attention`); the communication is the
+    same either way."""
     if pg is None or world == 1:
         return cp_attention(q, k, v, None, rank, 1, causal)
     out = _RingAttention.apply(
         q.transpose(1, 2).contiguous(),
         k.transpose(1, 2).contiguous(),
         v.transpose(1, 2).contiguous(),
-        pg, rank, world, causal,
+        pg, rank, world, causal, fused,
     )
     return out.transpose(1, 2)
 
