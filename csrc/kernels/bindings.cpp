@@ -33,22 +33,27 @@ int64_t blocks_of(const at::Tensor& t) {
   return (t.numel() + tft::kMtBlock - 1) / tft::kMtBlock;
 }
 
-// the pack of total_blocks blocks split over `world` slices
-PackGeom pack_geometry(int64_t total_blocks, int64_t world, const char* what) {
+// bytes of one block on the wire: the fp8 pack's fp32 scale and 2048 codes
+constexpr int64_t kFp8BlockBytes = 4 + tft::kMtBlock;
+
+// the pack of total_blocks blocks of block_bytes each split over `world` slices
+PackGeom pack_geometry(int64_t total_blocks, int64_t world, const char* what,
+                       int64_t block_bytes = kFp8BlockBytes) {
   TORCH_CHECK(world >= 1, what, ": world must be >= 1, got ", world);
   PackGeom g;
   g.total_blocks = total_blocks;
   g.padded_blocks = ((g.total_blocks + world - 1) / world) * world;
   g.blocks_per_rank = g.padded_blocks / world;
-  g.slice_bytes = g.blocks_per_rank * (4 + tft::kMtBlock);
+  g.slice_bytes = g.blocks_per_rank * block_bytes;
   return g;
 }
 
 // the pack whose tensor list is `tensors`
-PackGeom pack_geometry(const TensorList& tensors, int64_t world, const char* what) {
+PackGeom pack_geometry(const TensorList& tensors, int64_t world, const char* what,
+                       int64_t block_bytes = kFp8BlockBytes) {
   int64_t total_blocks = 0;
   for (auto& t : tensors) total_blocks += blocks_of(t);
-  return pack_geometry(total_blocks, world, what);
+  return pack_geometry(total_blocks, world, what, block_bytes);
 }
 
 // dtype_code of kernels.h, -1 for a dtype the multi-tensor kernels do not take
@@ -258,6 +263,70 @@ void fp8_reduce(at::Tensor recv, at::Tensor out, int64_t world, bool avg) {
   if (blocks_per_rank == 0) return;  // nothing but empty tensors: no launch
   tft::launch_reduce(recv.data_ptr<uint8_t>(), out.data_ptr<uint8_t>(), (int)world,
                      blocks_per_rank, slice_bytes, avg, current_stream());
+}
+
+// ---- MXFP4 quantized-collective support --------------------------------------
+// The fp8 trio's validation on a pack of kMxBlockBytes per block; the kernels
+// store dwords, so the pack must also start on a 4-byte boundary.
+
+namespace {
+
+void check_mx_aligned(const at::Tensor& buf, const char* what, const char* name) {
+  TORCH_CHECK(((int64_t)buf.data_ptr() & 3) == 0, what, ": ", name,
+              " does not start on a 4-byte boundary");
+}
+
+}  // namespace
+
+int64_t mxfp4_slice_bytes(const std::vector<at::Tensor>& tensors, int64_t world) {
+  return pack_geometry(tensors, world, "mxfp4_slice_bytes", tft::kMxBlockBytes).slice_bytes;
+}
+
+void mxfp4_quantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
+                    int64_t world) {
+  const char* what = "mxfp4_quantize";
+  const int code = first_dtype_code(tensors, what);
+  auto g = pack_geometry(tensors, world, what, tft::kMxBlockBytes);
+  TableSet tables(tensors[0], what, /*need_16b_alignment=*/true);
+  check_pack(pack, tensors, g, world, what);
+  check_mx_aligned(pack, what, "pack");
+  const int h = tables.add({{&tensors, tensors[0].scalar_type()}});
+  tables.upload();
+  tft::launch_mxfp4_quantize(code, tables.table(h), g.padded_blocks, g.blocks_per_rank,
+                             pack.data_ptr<uint8_t>(), current_stream());
+}
+
+void mxfp4_dequantize(const std::vector<at::Tensor>& tensors, at::Tensor pack,
+                      int64_t world) {
+  const char* what = "mxfp4_dequantize";
+  const int code = first_dtype_code(tensors, what);
+  auto g = pack_geometry(tensors, world, what, tft::kMxBlockBytes);
+  TableSet tables(tensors[0], what, /*need_16b_alignment=*/true);
+  check_pack(pack, tensors, g, world, what);
+  check_mx_aligned(pack, what, "pack");
+  const int h = tables.add({{&tensors, tensors[0].scalar_type()}});
+  tables.upload();
+  tft::launch_mxfp4_dequantize(code, tables.table(h), g.blocks_per_rank,
+                               pack.data_ptr<uint8_t>(), current_stream());
+}
+
+void mxfp4_reduce(at::Tensor recv, at::Tensor out, int64_t world, bool avg) {
+  TORCH_CHECK(recv.is_cuda() && recv.scalar_type() == at::kByte && recv.is_contiguous(),
+              "mxfp4_reduce: recv must be a contiguous uint8 device tensor");
+  TORCH_CHECK(out.device() == recv.device() && out.scalar_type() == at::kByte &&
+                  out.is_contiguous(),
+              "mxfp4_reduce: out must be a contiguous uint8 tensor on recv's device");
+  TORCH_CHECK(world >= 1, "mxfp4_reduce: world must be >= 1, got ", world);
+  TORCH_CHECK(recv.numel() == out.numel() * world,
+              "mxfp4_reduce: recv must hold world slices of out's size");
+  const int64_t blocks_per_rank = out.numel() / tft::kMxBlockBytes;
+  TORCH_CHECK(blocks_per_rank * tft::kMxBlockBytes == out.numel(),
+              "mxfp4_reduce: out is not a whole number of blocks");
+  if (blocks_per_rank == 0) return;  // nothing but empty tensors: no launch
+  check_mx_aligned(recv, "mxfp4_reduce", "recv");
+  check_mx_aligned(out, "mxfp4_reduce", "out");
+  tft::launch_mxfp4_reduce(recv.data_ptr<uint8_t>(), out.data_ptr<uint8_t>(), (int)world,
+                           blocks_per_rank, avg, current_stream());
 }
 
 // ---- fused model ops --------------------------------------------------------
@@ -1218,6 +1287,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fp8_quantize", &fp8_quantize);
   m.def("fp8_dequantize", &fp8_dequantize);
   m.def("fp8_reduce", &fp8_reduce);
+  m.def("mxfp4_slice_bytes", &mxfp4_slice_bytes);
+  m.def("mxfp4_quantize", &mxfp4_quantize,
+        "MXFP4 wire pack of the tensors: e8m0 scale per 32 elements, e2m1 codes");
+  m.def("mxfp4_dequantize", &mxfp4_dequantize);
+  m.def("mxfp4_reduce", &mxfp4_reduce,
+        "fp32 sum (or average) of world MXFP4 slices in rank order, requantized");
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("rope_apply", &rope_apply);

@@ -57,6 +57,20 @@ void launch_reduce(const uint8_t* in, uint8_t* out, int world,
                    int64_t blocks_per_rank, int64_t slice_bytes, bool avg,
                    tft_stream stream);
 
+// mxfp4_quant.hip ----------------------------------------------------------
+// The same three on the MXFP4 pack: per block 64 e8m0 scale bytes (one per
+// group of 32 elements) and 1024 bytes of e2m1 codes, so a slice is
+// blocks_per_rank * kMxBlockBytes bytes. Table and padding slots as above;
+// the pack, `in` and `out` must be 4 B-aligned. One wave per block: the grid
+// is a quarter of the blocks, rounded up.
+constexpr int kMxBlockBytes = 1088;
+void launch_mxfp4_quantize(int dtype_code, MultiTensorTable tb, int64_t padded_blocks,
+                           int64_t blocks_per_rank, uint8_t* pack, tft_stream stream);
+void launch_mxfp4_dequantize(int dtype_code, MultiTensorTable tb, int64_t blocks_per_rank,
+                             const uint8_t* pack, tft_stream stream);
+void launch_mxfp4_reduce(const uint8_t* in, uint8_t* out, int world,
+                         int64_t blocks_per_rank, bool avg, tft_stream stream);
+
 // fused_model_ops.hip ------------------------------------------------------
 // bf16 activations, weights and gradients, fp32 invrms and rotary tables, all
 // contiguous and 16 B-aligned (the bindings see to both); H % 8 == 0,

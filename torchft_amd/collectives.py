@@ -5,7 +5,9 @@ quantize → **alltoall** of per-rank slices → fused local reduce →
 **allgather** of the reduced slice → dequantize, cutting wire traffic ~4x
 at fp8 vs bf16 (8x vs fp32). On MI355X xGMI is 7 point-to-point links per
 GPU, so the alltoall+allgather decomposition engages all links instead of
-serializing on a single ring.
+serializing on a single ring. ``wire="mxfp4"`` sends e2m1 codes with one
+power-of-two scale byte per 32 elements instead (``csrc/kernels/mxfp4_quant.hip``):
+0.530 of the fp8 pack's bytes.
 
 ``allreduce_pack`` is the same exchange for a caller that already holds the
 quantized pack and decodes the result itself (the fused DiLoCo outer sync,
@@ -66,22 +68,38 @@ class _QuantizedWork(Work):
         return self._fut
 
 
+WIRES = {"fp8": "", "mxfp4": "mx_"}  # wire format -> prefix of its functions in quantization
+
+
+def _wire(wire: str):
+    """(geometry, quantize, reduce, dequantize) of a wire format, looked up in
+    ``quantization`` at call time."""
+    if wire not in WIRES:
+        raise ValueError(f"unknown wire format {wire!r}: expected one of {sorted(WIRES)}")
+    return tuple(getattr(Q, WIRES[wire] + name) for name in
+                 ("pack_geometry", "quantize_pack", "reduce_slices", "dequantize_pack"))
+
+
 def allreduce_quantized(
     tensors: List[torch.Tensor],
     op: ReduceOp,
     pg: ProcessGroup,
     sync_stream: Optional[torch.cuda.Stream] = None,
+    wire: str = "fp8",
 ) -> Work:
-    """Fault-tolerant fp8 allreduce of ``tensors`` (in place).
+    """Fault-tolerant quantized allreduce of ``tensors`` (in place).
 
-    op must be SUM or AVG (AVG folds 1/world into the requantization scale
-    inside the fused reduce kernel — no extra pass).
+    op must be SUM or AVG (the fused reduce kernel applies 1/world itself —
+    no extra pass). ``wire`` is the format that travels: ``"fp8"`` (e4m3 in
+    2048-element blocks, 8.02 bits per element) or ``"mxfp4"`` (e2m1 codes
+    with one power-of-two scale byte per 32 elements, 4.25 bits per element).
     """
     assert torch.cuda.is_available(), "quantized allreduce requires a HIP device"
     world = pg.size()
     avg = op == ReduceOp.AVG
+    geometry, quantize, reduce, dequantize = _wire(wire)
 
-    _, _, _, slice_bytes = Q.pack_geometry(tensors, world)
+    _, _, _, slice_bytes = geometry(tensors, world)
     device = tensors[0].device
 
     if sync_stream is None:
@@ -93,14 +111,14 @@ def allreduce_quantized(
 
     with torch.cuda.stream(sync_stream):
         pack = torch.empty(world * slice_bytes, dtype=torch.uint8, device=device)
-        Q.quantize_pack(tensors, pack, world)
+        quantize(tensors, pack, world)
 
         recv = torch.empty_like(pack)  # world copies of OUR slice
         a2a_work = pg.alltoall_base(recv, pack, [], [], AllToAllOptions())
         a2a_work.wait()
 
         my_slice = pack.narrow(0, 0, slice_bytes)  # reuse pack's first slice slot
-        Q.reduce_slices(recv.view(world, slice_bytes).view(-1), my_slice, world, avg)
+        reduce(recv.view(world, slice_bytes).view(-1), my_slice, world, avg)
 
         ag_work = pg.allgather_into_tensor_coalesced([pack], [my_slice.clone()],
                                                      AllgatherOptions())
@@ -109,7 +127,7 @@ def allreduce_quantized(
         def _dequant(f: Future) -> List[torch.Tensor]:
             with torch.cuda.stream(sync_stream):
                 f.wait()
-                Q.dequantize_pack(tensors, pack, world)
+                dequantize(tensors, pack, world)
             return tensors
 
         fut = fut.then(_dequant)
@@ -168,16 +186,18 @@ def reduce_scatter_quantized(
     op: ReduceOp,
     pg: ProcessGroup,
     sync_stream: Optional[torch.cuda.Stream] = None,
+    wire: str = "fp8",
 ) -> tuple[Work, torch.Tensor]:
-    """fp8 reduce-scatter: returns (work, out) where ``out`` is this rank's
-    reduced share — ``blocks_per_rank * QBLOCK`` elements of the
+    """Quantized reduce-scatter: returns (work, out) where ``out`` is this
+    rank's reduced share — ``blocks_per_rank * QBLOCK`` elements of the
     block-padded concatenation of ``tensors``, dequantized to the input
-    dtype (zero-padded tail)."""
+    dtype (zero-padded tail). ``wire`` as in ``allreduce_quantized``."""
     assert torch.cuda.is_available(), "quantized reduce_scatter requires a HIP device"
     world = pg.size()
     avg = op == ReduceOp.AVG
+    geometry, quantize, reduce, dequantize = _wire(wire)
 
-    _, _, bpr, slice_bytes = Q.pack_geometry(tensors, world)
+    _, _, bpr, slice_bytes = geometry(tensors, world)
     device = tensors[0].device
     if sync_stream is None:
         sync_stream = torch.cuda.Stream()
@@ -187,15 +207,15 @@ def reduce_scatter_quantized(
 
     with torch.cuda.stream(sync_stream):
         pack = torch.empty(world * slice_bytes, dtype=torch.uint8, device=device)
-        Q.quantize_pack(tensors, pack, world)
+        quantize(tensors, pack, world)
 
         recv = torch.empty_like(pack)
         pg.alltoall_base(recv, pack, [], [], AllToAllOptions()).wait()
 
         my_slice = torch.empty(slice_bytes, dtype=torch.uint8, device=device)
-        Q.reduce_slices(recv, my_slice, world, avg)
+        reduce(recv, my_slice, world, avg)
         # dequantize only our slice into the flat output
-        Q.dequantize_pack([out], my_slice, 1)
+        dequantize([out], my_slice, 1)
 
         fut: Future = Future()
         fut.set_result([out])

@@ -55,7 +55,7 @@ try:
 except ImportError:  # pragma: no cover
     DTensor = None  # type: ignore[assignment]
 
-from torchft_amd.manager import Manager
+from torchft_amd.manager import Manager, quantize_wire
 
 logger: logging.Logger = logging.getLogger(__name__)
 
@@ -356,7 +356,7 @@ class _StreamingDiLoCoFragment:
         pin_memory: bool = True,
         use_bucketization: bool = False,
         bucket_cap_mb: Optional[int] = None,
-        should_quantize: bool = False,
+        should_quantize: bool | str = False,
         fragment_sync_delay: int = 0,
         fragment_update_alpha: float = 0.0,
         fused_sync: bool = False,
@@ -368,6 +368,12 @@ class _StreamingDiLoCoFragment:
         if fused_fp8_pack and not (fused_sync and should_quantize):
             raise ValueError(
                 "fused_fp8_pack needs fused_sync=True and should_quantize=True"
+            )
+        # refuses an unknown wire format whether or not the pack is fused
+        if quantize_wire(should_quantize) != "fp8" and fused_fp8_pack:
+            raise ValueError(
+                "fused_fp8_pack keeps the pseudo-gradient in the fp8 pack: it needs "
+                f"should_quantize=True, not {should_quantize!r}"
             )
 
         self._fused_fp8_pack = fused_fp8_pack
@@ -834,6 +840,11 @@ class DiLoCo:
     (``ops.pseudograd_fp8_``), ``Manager.allreduce_pack`` reduces the pack in
     place, and the outer step decodes it (``ops.diloco_outer_step_fp8_``). The
     parameters and their snapshots must start on 16 B boundaries.
+
+    ``should_quantize="mxfp4"`` sends the pseudo-gradients in the 4.25-bit
+    MXFP4 wire pack (``Manager.allreduce``) where ``True`` sends fp8; any other
+    string raises ``ValueError``, and so does ``"mxfp4"`` with
+    ``fused_fp8_pack=True``: the fused pack is fp8.
     """
 
     def __init__(
@@ -847,7 +858,7 @@ class DiLoCo:
         pin_memory: bool = True,
         use_bucketization: bool = False,
         bucket_cap_mb: Optional[int] = None,
-        should_quantize: bool = False,
+        should_quantize: bool | str = False,
         fragment_sync_delay: int = 0,
         fragment_update_alpha: float = 0.0,
         fused_sync: bool = False,

@@ -86,6 +86,20 @@ def extract_trailing_digits(s: str) -> int:
     return int(digits) if digits else 0
 
 
+def quantize_wire(should_quantize: bool | str) -> Optional[str]:
+    """The wire format a ``should_quantize`` value asks for
+    (``collectives.allreduce_quantized(wire=)``): ``None`` for a false value,
+    ``"fp8"`` for ``True``, ``"mxfp4"`` for that string; any other string is a
+    ``ValueError``."""
+    if isinstance(should_quantize, str):
+        if should_quantize != "mxfp4":
+            raise ValueError(
+                f"should_quantize must be a bool or 'mxfp4', got {should_quantize!r}"
+            )
+        return "mxfp4"
+    return "fp8" if should_quantize else None
+
+
 class WorldSizeMode(Enum):
     """Numeric handling of a changing replica count.
 
@@ -263,8 +277,9 @@ class Manager:
         init_sync: bool = True,
         max_retries: Optional[int] = None,
         quorum_retries: int = 0,
-        should_quantize: bool = False,
+        should_quantize: bool | str = False,
     ) -> None:
+        quantize_wire(should_quantize)  # refuses an unknown wire format here
         # telemetry channels (structured records; see telemetry.py)
         self.quorum_logger: logging.Logger = logging.getLogger("torchft_quorums")
         self.commits_logger: logging.Logger = logging.getLogger("torchft_commits")
@@ -428,7 +443,7 @@ class Manager:
     def allreduce(
         self,
         tensor: torch.Tensor,
-        should_quantize: Optional[bool] = None,
+        should_quantize: Optional[bool | str] = None,
         reduce_op: ReduceOp = ReduceOp.AVG,
     ) -> Work:
         """Fault-tolerant allreduce of ``tensor``.
@@ -440,10 +455,12 @@ class Manager:
 
         ``should_quantize=True`` takes the fp8 path: CDNA4 quantize kernels
         plus an alltoall/allgather decomposition that engages all 7 xGMI
-        links.
+        links. ``should_quantize="mxfp4"`` takes the same path with the
+        4.25-bit MXFP4 wire pack; any other string is a ``ValueError``.
         """
         if should_quantize is None:
             should_quantize = self._default_should_quantize
+        wire = quantize_wire(should_quantize)
 
         if self.errored():
             return _DummyWork(tensor)
@@ -465,7 +482,7 @@ class Manager:
                 from torchft_amd.collectives import allreduce_quantized
 
                 work = allreduce_quantized(
-                    [tensor], wire_op, self._pg, torch.cuda.current_stream()
+                    [tensor], wire_op, self._pg, torch.cuda.current_stream(), wire=wire
                 )
             else:
                 opts = AllreduceOptions()

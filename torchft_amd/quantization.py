@@ -11,6 +11,10 @@ Blocks are 2048 elements; each tensor is padded to whole blocks so a block
 never straddles tensors. Reference analogue: torchft/quantization.py
 (Triton, per-row striping) — re-designed block-wise for MI355X (see the .hip
 header comment).
+
+The ``mx_*`` functions further down are the same wrappers and reference for
+the MXFP4 pack of ``csrc/kernels/mxfp4_quant.hip``: the same blocks, 4.25 bits
+per element.
 """
 
 from __future__ import annotations
@@ -183,3 +187,146 @@ def reduce_slices_ref(recv: torch.Tensor, world: int, avg: bool,
     inv_div = float(torch.tensor(1.0, dtype=torch.float32) / world) if avg else 1.0
     _, q, dq = block_scales_ref(acc, inv_div)
     return _write_slices(dq, e4m3_codes(acc * q[:, None]), 1)
+
+
+# ------------------------------------------------------------------- MXFP4
+#
+# The 4.25-bit wire pack of csrc/kernels/mxfp4_quant.hip. Blocks, padding and
+# slicing are the fp8 pack's; inside a block, 64 groups of MX_GROUP consecutive
+# elements share one e8m0 scale byte (2^X, stored as X + 127) and an element
+# is one e2m1 code: bit 3 the sign, bits 0-2 an index into E2M1_GRID; element
+# 2i of a group in the low nibble of code byte i, element 2i + 1 in the high
+# one. Slice r = [64 scale bytes per block] ‖ [1024 code bytes per block].
+
+MX_GROUP = 32
+MX_GROUPS = QBLOCK // MX_GROUP  # scale bytes of a block
+MX_BLOCK_BYTES = MX_GROUPS + QBLOCK // 2  # 1088
+MX_NAN_SCALE = 0xFF  # a group that held a NaN or an Inf: decodes to NaN
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx_pack_geometry(tensors: List[torch.Tensor], world: int) -> Tuple[int, int, int, int]:
+    """Returns (total_blocks, padded_blocks, blocks_per_rank, slice_bytes)."""
+    total, padded, bpr, _ = pack_geometry(tensors, world)
+    return total, padded, bpr, bpr * MX_BLOCK_BYTES
+
+
+def mx_quantize_pack(tensors: List[torch.Tensor], pack: torch.Tensor, world: int) -> None:
+    hip_ext().mxfp4_quantize(tensors, pack, world)
+
+
+def mx_dequantize_pack(tensors: List[torch.Tensor], pack: torch.Tensor, world: int) -> None:
+    hip_ext().mxfp4_dequantize(tensors, pack, world)
+
+
+def mx_reduce_slices(recv: torch.Tensor, out: torch.Tensor, world: int, avg: bool) -> None:
+    hip_ext().mxfp4_reduce(recv, out, world, avg)
+
+
+# The reference, from the format's definition in fp32 torch on the CPU: the
+# exponent bits for X, thresholds with the tie rule for the codes. Every
+# product with 2^X or 2^-X is exact, so there is one right answer per byte.
+
+
+def _pow2(biased: torch.Tensor) -> torch.Tensor:
+    """2^(biased - 127) as fp32 from its exponent field, 1 <= biased <= 254."""
+    return (biased.to(torch.int32) << 23).view(torch.float32)
+
+
+def mx_encode_ref(blocks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[n, QBLOCK] fp32 -> ([n, MX_GROUPS] scale bytes, [n, QBLOCK // 2] code
+    bytes). Per group: amax over the elements (a NaN or an Inf anywhere makes
+    the byte MX_NAN_SCALE and the codes zero), X = clamp(floor(log2 amax) - 2,
+    -125, 125) read from amax's exponent field, so zero and subnormal amax take
+    the lower clamp; code = |v| * 2^-X rounded to E2M1_GRID, nearest, a tie to
+    the even code, above 6 to 6, with v's sign (of -0 too) in bit 3."""
+    g = blocks.float().reshape(-1, MX_GROUP)
+    bad = ~torch.isfinite(g).all(dim=1)
+    amax = torch.where(bad[:, None], torch.zeros_like(g), g.abs()).amax(dim=1)
+    field = (amax.view(torch.int32) >> 23) & 0xFF
+    byte = (field - 2).clamp(2, 252)  # X + 127
+    y = g.abs() * _pow2(254 - byte)[:, None]  # |v| * 2^-X
+    # midpoints of neighbouring grid values; a tie goes to the even code
+    code = ((y > 0.25).int() + (y >= 0.75).int() + (y > 1.25).int() + (y >= 1.75).int()
+            + (y > 2.5).int() + (y >= 3.5).int() + (y > 5.0).int())
+    code = code | (torch.signbit(g).int() << 3)
+    code = torch.where(bad[:, None], torch.zeros_like(code), code).to(torch.uint8)
+    byte = torch.where(bad, torch.full_like(byte, MX_NAN_SCALE), byte).to(torch.uint8)
+    pairs = code.reshape(-1, 2)
+    packed = pairs[:, 0] | (pairs[:, 1] << 4)
+    n = blocks.shape[0]
+    return byte.reshape(n, MX_GROUPS), packed.reshape(n, QBLOCK // 2)
+
+
+def mx_decode_ref(scales: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """([..., MX_GROUPS] scale bytes, [..., QBLOCK // 2] code bytes) -> fp32
+    [..., QBLOCK]: ``E2M1_GRID[code & 7] * 2^X`` with the sign, NaN for a group
+    whose scale byte is MX_NAN_SCALE."""
+    c = torch.stack([codes & 0xF, codes >> 4], dim=-1).reshape(*codes.shape[:-1], QBLOCK)
+    mag = torch.tensor(E2M1_GRID, dtype=torch.float32, device=codes.device)[(c & 7).long()]
+    val = torch.where((c & 8) != 0, -mag, mag)
+    s = scales.to(torch.int32)
+    # byte 0 is 2^-127, below the exponent field's range
+    scale = torch.where(s == 0, torch.full_like(s, 0x00400000), s << 23).view(torch.float32)
+    scale = torch.where(s == MX_NAN_SCALE, torch.full_like(scale, float("nan")), scale)
+    return val * scale.repeat_interleave(MX_GROUP, dim=-1)
+
+
+def _mx_write_slices(scales: torch.Tensor, codes: torch.Tensor, world: int) -> torch.Tensor:
+    bpr = scales.shape[0] // world if world else 0
+    return torch.cat([scales.reshape(world, bpr * MX_GROUPS),
+                      codes.reshape(world, bpr * (QBLOCK // 2))], dim=1).reshape(-1)
+
+
+def mx_split_slices(pack: torch.Tensor, slices: int):
+    """A buffer of `slices` equal slices -> ([slices, bpr, MX_GROUPS] scale
+    bytes, [slices, bpr, QBLOCK // 2] code bytes)."""
+    slice_bytes = pack.numel() // slices if slices else 0
+    bpr = slice_bytes // MX_BLOCK_BYTES
+    sl = pack.view(slices, slice_bytes)
+    return (sl[:, : bpr * MX_GROUPS].reshape(slices, bpr, MX_GROUPS),
+            sl[:, bpr * MX_GROUPS:].reshape(slices, bpr, QBLOCK // 2))
+
+
+def mx_quantize_pack_ref(tensors: List[torch.Tensor], world: int) -> torch.Tensor:
+    """The MXFP4 wire buffer of `tensors`, every byte of it: the padding of a
+    tensor's last block and the padding blocks of the last slice are zeros
+    under the same rule (scale byte 2, zero codes)."""
+    _, padded, _, _ = mx_pack_geometry(tensors, world)
+    allb = torch.zeros(padded, QBLOCK, dtype=torch.float32, device=tensors[0].device)
+    b = 0
+    for t in tensors:
+        flat = t.detach().float().reshape(-1)
+        nb = (flat.numel() + QBLOCK - 1) // QBLOCK
+        allb[b : b + nb].view(-1)[: flat.numel()] = flat
+        b += nb
+    return _mx_write_slices(*mx_encode_ref(allb), world)
+
+
+def mx_dequantize_pack_ref(
+    shapes_numels: List[int], pack: torch.Tensor, world: int
+) -> List[torch.Tensor]:
+    """Decode an MXFP4 buffer into flat fp32 tensors of the given numels."""
+    scales, codes = mx_split_slices(pack, world)
+    vals = mx_decode_ref(scales.reshape(-1, MX_GROUPS), codes.reshape(-1, QBLOCK // 2))
+    out = []
+    b = 0
+    for n in shapes_numels:
+        nb = (n + QBLOCK - 1) // QBLOCK
+        out.append(vals[b : b + nb].reshape(-1)[:n].clone())
+        b += nb
+    return out
+
+
+def mx_reduce_slices_ref(recv: torch.Tensor, world: int, avg: bool) -> torch.Tensor:
+    """The fused reduce on `world` received slices: fp32 accumulation of the
+    decoded values in rank order from zero, for AVG one product with
+    fl(1/world), then the quantizer's rule. A NaN scale byte from any rank
+    makes the group NaN."""
+    scales, codes = mx_split_slices(recv, world)
+    acc = torch.zeros(codes.shape[1], QBLOCK, dtype=torch.float32, device=recv.device)
+    for r in range(world):
+        acc = acc + mx_decode_ref(scales[r], codes[r])
+    if avg:
+        acc = acc * (torch.tensor(1.0, dtype=torch.float32, device=recv.device) / world)
+    return _mx_write_slices(*mx_encode_ref(acc), 1)
